@@ -11,7 +11,15 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-One JSON line on rank 0; `value` is the WHOLE-JOB total images/sec.
+One JSON line on rank 0; `value` is the WHOLE-JOB total images/sec and
+`ms_per_step` the wall time of one of the K timed steps.
+
+A plain run only sets up, warms up, times the K steps and prints the result
+line.  `--dump-outputs DIR` additionally writes what the last timed step
+computed (loss.npy, logits.npy, params.npy — float32; the model, data and
+sample indices are seeded, so two builds compare output for output).
+`--full` is reserved for measurements beyond the headline figure; there are
+none today, so it changes nothing.
 """
 import argparse
 import json
@@ -55,7 +63,47 @@ def parse_args():
                    help="capture forward+backward in a hipGraph; allreduce + "
                         "optimizer run after replay (trades overlap for "
                         "launch overhead)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, logits, updated parameters) "
+                        "as DIR/<name>.npy (float32; outputs larger than "
+                        "the per-array cap are a fixed seeded sample)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements and checks beyond the "
+                        "headline figure (there are none today: a plain run "
+                        "already does only setup, warmup and the timed "
+                        "steps; secondary configs are selected explicitly "
+                        "with the flags above)")
     return p.parse_args()
+
+
+# --dump-outputs: at most this many elements per array (float32 -> 16 MiB
+# each, three arrays -> well under 64 MB in all)
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+DUMP_SAMPLE_SEED = 1234
+
+
+def _dump_array(t):
+    """float32 numpy copy of tensor `t`; tensors above DUMP_MAX_ELEMS are
+    reduced to a fixed, seeded sample of their flattened elements (same
+    indices for the same shape, so two builds compare element for element)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g)
+        idx = idx.sort().values.to(flat.device)
+        return flat[idx].float().cpu().numpy()
+    return t.detach().float().cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = torch.cat([p.detach().reshape(-1).float()
+                        for p in model.parameters()])
+    for name, t in (("loss", loss), ("logits", logits), ("params", params)):
+        np.save(os.path.join(out_dir, name + ".npy"), _dump_array(t))
 
 
 def main():
@@ -128,9 +176,10 @@ def main():
 
         def fwd_bwd():
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_bf16):
-                loss = loss_fn(model(data), target)
+                logits = model(data)
+                loss = loss_fn(logits, target)
             loss.backward()
-            return loss
+            return loss.detach(), logits.detach()
 
         # warm up allocator state on a side stream, then capture
         s = torch.cuda.Stream()
@@ -145,7 +194,7 @@ def main():
         for p in params:
             p.grad.zero_()
         with torch.cuda.graph(graph):
-            fwd_bwd()
+            static_out = fwd_bwd()
         grads = [p.grad for p in params]
 
         from horovod_amd.torch import mpi_ops as _ops
@@ -161,6 +210,7 @@ def main():
             opt.step()
             for g in grads:
                 g.zero_()
+            return static_out
     else:
         opt = hvd.DistributedOptimizer(
             opt, named_parameters=model.named_parameters(),
@@ -173,12 +223,14 @@ def main():
             opt.zero_grad()
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_bf16):
                 if is_bert:
-                    mlm, _ = model(data)
-                    loss = loss_fn(mlm.flatten(0, 1), target.flatten())
+                    logits, _ = model(data)
+                    loss = loss_fn(logits.flatten(0, 1), target.flatten())
                 else:
-                    loss = loss_fn(model(data), target)
+                    logits = model(data)
+                    loss = loss_fn(logits, target)
             loss.backward()
             opt.step()
+            return loss.detach(), logits.detach()
 
     for _ in range(args.warmup):
         step()
@@ -186,9 +238,10 @@ def main():
     hvd.barrier()
     if cuda:
         torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     if cuda:
         torch.cuda.synchronize()
     hvd.barrier()
@@ -197,6 +250,11 @@ def main():
     elapsed_t = torch.tensor([elapsed], dtype=torch.float64)
     elapsed = float(hvd.allreduce(elapsed_t, op=hvd.Max,
                                   name="bench_elapsed").item())
+
+    if args.dump_outputs and hvd.rank() == 0:
+        if last is None:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        dump_outputs(args.dump_outputs, last[0], last[1], model)
 
     n = hvd.size()
     total_images = n * batch * args.steps

@@ -35,6 +35,43 @@ def test_bench_contract_torchrun_np2():
     assert res["data"] == "synthetic"
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's loss, logits and
+    (sampled) parameters as float32 .npy files; the model, data and sample
+    indices are seeded, so two runs with the same arguments agree (to fp32
+    reduction-order noise).  `--full` is accepted and `--steps` is the
+    number of timed steps reported next to `ms_per_step`."""
+    import numpy as np
+
+    # the CPU path (fp32, deterministic kernels) on every box: hide any GPU
+    env = _env()
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = ""
+
+    def run(out):
+        r = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+             "--steps", "2", "--warmup", "1", "--full",
+             "--dump-outputs", str(out)],
+            env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(line) == 1, r.stdout
+        res = json.loads(line[0])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0
+        assert res["value"] > 0
+        return {f: np.load(out / f) for f in sorted(os.listdir(out))}
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    assert sorted(a) == ["logits.npy", "loss.npy", "params.npy"]
+    assert sum(x.nbytes for x in a.values()) <= 64 * 1000 * 1000
+    for name in a:
+        assert a[name].dtype == np.float32, name
+        assert np.isfinite(a[name]).all(), name
+        assert a[name].shape == b[name].shape, name
+        assert np.allclose(a[name], b[name], rtol=1e-4, atol=1e-5), name
+    assert a["loss.npy"].shape == () and a["logits.npy"].shape[1] == 1000
+
+
 def test_mnist_example_np2():
     r = subprocess.run(
         [sys.executable, os.path.join(REPO, "bin", "hvdrun"), "-np", "2",
