@@ -163,6 +163,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                                need_res);
         });
 
+  // ---- SyncBatchNorm passes (None = absent optional tensor) ----------------
+  m.def("sync_bn_stats",
+        [](at::Tensor x) { return hvd::gpu::SyncBnStats(x); });
+  m.def("sync_bn_normalize",
+        [](at::Tensor x, at::Tensor stats, py::object weight, py::object bias,
+           py::object rm, py::object rv, double momentum, double eps) {
+          auto opt = [](const py::object& o) {
+            return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
+          };
+          return hvd::gpu::SyncBnNormalize(x, stats, opt(weight), opt(bias),
+                                           opt(rm), opt(rv), momentum, eps);
+        });
+  m.def("sync_bn_backward_reduce",
+        [](at::Tensor x, at::Tensor dy, at::Tensor mean, at::Tensor invstd) {
+          return hvd::gpu::SyncBnBackwardReduce(x, dy, mean, invstd);
+        });
+  m.def("sync_bn_backward_apply",
+        [](at::Tensor x, at::Tensor dy, at::Tensor mean, at::Tensor invstd,
+           py::object weight, at::Tensor sums, at::Tensor count) {
+          at::Tensor w;
+          if (!weight.is_none()) w = weight.cast<at::Tensor>();
+          return hvd::gpu::SyncBnBackwardApply(x, dy, mean, invstd, w, sums,
+                                               count);
+        });
+
   // ---- timeline -----------------------------------------------------------
   m.def("start_timeline", [](const std::string& path, bool mark_cycles) {
     auto& st = State();

@@ -10,31 +10,13 @@
 // with C contiguous and C % 8 == 0 (every ResNet channel width).  Stats
 // accumulate in fp32 via per-block LDS bins (C <= 4096 -> <= 32 KB LDS)
 // flushed with one global atomicAdd per channel per block (guide G12).
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_bf16.h>
-
-#include <algorithm>
-
+#include "bn_common.h"
 #include "kernels.h"
 
 namespace hvd {
 namespace gpu {
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ float to_f(T v) { return (float)v; }
-template <>
-__device__ __forceinline__ float to_f<__hip_bfloat16>(__hip_bfloat16 v) {
-  return __bfloat162float(v);
-}
-template <typename T>
-__device__ __forceinline__ T from_f(float v) { return (T)v; }
-template <>
-__device__ __forceinline__ __hip_bfloat16 from_f<__hip_bfloat16>(float v) {
-  return __float2bfloat16(v);
-}
 
 // ---- forward stats: per-channel sum and sum-of-squares --------------------
 // Fixed-channel decomposition: the host sizes the grid so
@@ -294,26 +276,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(
       ((uint4*)dx)[i * 2 + 1] = ((uint4*)&vo)[1];
     }
   }
-}
-
-int grid_for(long long total, int C, int vecs_per_thread = 1) {
-  // vecs_per_thread > 1 for the REDUCTION kernels: their per-block flush
-  // costs 2*C global atomicAdds, so wide-channel shapes with few rows must
-  // amortize it over more elements per block (measured: at C=2048, N*H*W
-  // = 3136 the old 1-vec grid issued ~1.3 atomics PER ELEMENT and lost
-  // ~40% to MIOpen; 8 vecs/thread cuts the flush traffic 8x).  Elementwise
-  // kernels keep 1 for maximum bandwidth-filling parallelism.
-  long long blocks = (total / 8 + 256LL * vecs_per_thread - 1) /
-                     (256LL * vecs_per_thread);
-  blocks = std::min<long long>(blocks > 0 ? blocks : 1, 2048);
-  // fixed-channel decomposition invariant: (blocks*256*8) % C == 0 so each
-  // thread's channel octet is stride-invariant.  vecs_per_row = C/8 <= 512;
-  // round blocks up to a multiple of ceil(C/8/256) and ensure divisibility.
-  long long vpr = C / 8;  // vectors per row
-  long long g = std::__gcd((long long)256, vpr);
-  long long mult = vpr / g;  // blocks must be a multiple of this
-  blocks = ((blocks + mult - 1) / mult) * mult;
-  return (int)blocks;
 }
 
 }  // namespace

@@ -1715,6 +1715,202 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
   return out;
 }
 
+// ---- SyncBatchNorm host side -----------------------------------------------
+// The four passes around the two stats allreduces; see syncbn_kernels.hip.
+// All on torch's current stream, no host read-back: the global count stays
+// on the device as the last word of the stats buffer.
+namespace {
+
+struct SbnShape {
+  int64_t outer, C, inner;
+  bool channels_last;
+  at::MemoryFormat format;
+};
+
+SbnShape SyncBnShape(const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "sync_bn: expected a GPU tensor");
+  TORCH_CHECK(x.dim() >= 2 && x.numel() > 0,
+              "sync_bn: expected a non-empty input of at least 2 dims");
+  auto st = x.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16,
+              "sync_bn: input must be fp32, fp16 or bf16");
+  SbnShape s;
+  s.C = x.size(1);
+  s.format = at::MemoryFormat::Contiguous;
+  s.channels_last = false;
+  if (!x.is_contiguous()) {
+    if (x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast)) {
+      s.format = at::MemoryFormat::ChannelsLast;
+    } else if (x.dim() == 5 &&
+               x.is_contiguous(at::MemoryFormat::ChannelsLast3d)) {
+      s.format = at::MemoryFormat::ChannelsLast3d;
+    } else {
+      TORCH_CHECK(false,
+                  "sync_bn: input must be contiguous or channels_last");
+    }
+    s.channels_last = true;
+  }
+  if (s.channels_last) {
+    s.outer = x.numel() / s.C;
+    s.inner = 1;
+  } else {
+    s.outer = x.size(0);
+    s.inner = x.numel() / (s.outer * s.C);
+  }
+  TORCH_CHECK(x.numel() / s.C < (1LL << 24),
+              "sync_bn: per-channel element count must stay below 2^24");
+  return s;
+}
+
+at::Tensor SbnF32(const at::Tensor& t) {
+  return t.scalar_type() == at::kFloat && t.is_contiguous()
+             ? t
+             : t.to(at::kFloat).contiguous();
+}
+
+void SbnCheckVec(const at::Tensor& t, int64_t n, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == n,
+              "sync_bn: ", what, " must be a contiguous fp32 GPU tensor of ",
+              n, " elements");
+}
+
+at::Tensor SbnBanks(const SbnShape& s, const at::TensorOptions& fopts) {
+  if (!SyncBnBanked(s.C, s.inner)) return at::Tensor();
+  return at::empty({(int64_t)kBnBanks * 2 * s.C}, fopts);
+}
+
+}  // namespace
+
+at::Tensor SyncBnStats(at::Tensor x) {
+  SbnShape s = SyncBnShape(x);
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
+  at::Tensor out = at::empty({2 * s.C + 1}, fopts);
+  at::Tensor banks = SbnBanks(s, fopts);
+  HIP_CHECK(SyncBnStatsLaunch(
+      x.data_ptr(), s.outer, s.C, s.inner,
+      (int)DataTypeFromTorch(x.scalar_type()),
+      banks.defined() ? banks.data_ptr<float>() : nullptr,
+      out.data_ptr<float>(), stream));
+  return out;
+}
+
+// Returns {y, mean, invstd}; stats is the allreduced [sum, sqsum, count].
+std::vector<at::Tensor> SyncBnNormalize(at::Tensor x, at::Tensor stats,
+                                        at::Tensor weight, at::Tensor bias,
+                                        at::Tensor running_mean,
+                                        at::Tensor running_var,
+                                        double momentum, double eps) {
+  SbnShape s = SyncBnShape(x);
+  const int64_t C = s.C;
+  SbnCheckVec(stats, 2 * C + 1, "stats");
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
+  at::Tensor mi = at::empty({2 * C}, fopts);
+  at::Tensor mean = mi.narrow(0, 0, C), invstd = mi.narrow(0, C, C);
+  bool has_running = running_mean.defined() && running_var.defined();
+  bool stats_f32 = has_running &&
+                   running_mean.scalar_type() == at::kFloat &&
+                   running_mean.is_contiguous() &&
+                   running_var.scalar_type() == at::kFloat &&
+                   running_var.is_contiguous();
+  if (has_running)
+    TORCH_CHECK(running_mean.numel() == C && running_var.numel() == C,
+                "sync_bn: running stats must have C elements");
+  HIP_CHECK(SyncBnFinalizeLaunch(
+      stats.data_ptr<float>(), mean.data_ptr<float>(),
+      invstd.data_ptr<float>(),
+      stats_f32 ? running_mean.data_ptr<float>() : nullptr,
+      stats_f32 ? running_var.data_ptr<float>() : nullptr, (float)momentum,
+      (float)eps, (int)C, stream));
+  if (has_running && !stats_f32) {
+    // rare non-fp32 running stats: fall back to ATen for the update only
+    at::Tensor n = stats.narrow(0, 2 * C, 1);
+    at::Tensor var = (at::pow(invstd, -2) - eps).clamp_min(0);
+    at::Tensor ub = n / (n - 1).clamp_min(1);
+    running_mean.mul_(1 - momentum).add_(mean.to(running_mean.scalar_type()),
+                                         momentum);
+    running_var.mul_(1 - momentum)
+        .add_((var * ub).to(running_var.scalar_type()), momentum);
+  }
+  at::Tensor w_f, b_f;
+  if (weight.defined()) {
+    w_f = SbnF32(weight);
+    SbnCheckVec(w_f, C, "weight");
+  }
+  if (bias.defined()) {
+    b_f = SbnF32(bias);
+    SbnCheckVec(b_f, C, "bias");
+  }
+  at::Tensor y = at::empty_like(x);
+  HIP_CHECK(SyncBnApplyLaunch(
+      x.data_ptr(), y.data_ptr(), mean.data_ptr<float>(),
+      invstd.data_ptr<float>(),
+      w_f.defined() ? w_f.data_ptr<float>() : nullptr,
+      b_f.defined() ? b_f.data_ptr<float>() : nullptr, s.outer, C, s.inner,
+      (int)DataTypeFromTorch(x.scalar_type()), stream));
+  return {y, mean, invstd};
+}
+
+at::Tensor SyncBnBackwardReduce(at::Tensor x, at::Tensor dy, at::Tensor mean,
+                                at::Tensor invstd) {
+  SbnShape s = SyncBnShape(x);
+  const int64_t C = s.C;
+  SbnCheckVec(mean, C, "mean");
+  SbnCheckVec(invstd, C, "invstd");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type(),
+              "sync_bn: grad_output must match the input's shape and dtype");
+  dy = dy.contiguous(s.format);
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
+  at::Tensor out = at::empty({2 * C}, fopts);
+  at::Tensor banks = SbnBanks(s, fopts);
+  HIP_CHECK(SyncBnBwdReduceLaunch(
+      x.data_ptr(), dy.data_ptr(), mean.data_ptr<float>(),
+      invstd.data_ptr<float>(), s.outer, C, s.inner,
+      (int)DataTypeFromTorch(x.scalar_type()),
+      banks.defined() ? banks.data_ptr<float>() : nullptr,
+      out.data_ptr<float>(), stream));
+  return out;
+}
+
+at::Tensor SyncBnBackwardApply(at::Tensor x, at::Tensor dy, at::Tensor mean,
+                               at::Tensor invstd, at::Tensor weight,
+                               at::Tensor sums, at::Tensor count) {
+  SbnShape s = SyncBnShape(x);
+  const int64_t C = s.C;
+  SbnCheckVec(mean, C, "mean");
+  SbnCheckVec(invstd, C, "invstd");
+  SbnCheckVec(sums, 2 * C, "sums");
+  SbnCheckVec(count, 1, "count");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type(),
+              "sync_bn: grad_output must match the input's shape and dtype");
+  dy = dy.contiguous(s.format);
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  at::Tensor w_f;
+  if (weight.defined()) {
+    w_f = SbnF32(weight);
+    SbnCheckVec(w_f, C, "weight");
+  }
+  at::Tensor dx = at::empty_like(x);
+  HIP_CHECK(SyncBnBwdApplyLaunch(
+      x.data_ptr(), dy.data_ptr(), dx.data_ptr(), mean.data_ptr<float>(),
+      invstd.data_ptr<float>(),
+      w_f.defined() ? w_f.data_ptr<float>() : nullptr,
+      sums.data_ptr<float>(), count.data_ptr<float>(), s.outer, C, s.inner,
+      (int)DataTypeFromTorch(x.scalar_type()), stream));
+  return dx;
+}
+
 void WaitAllPending() {
   while (true) {
     {

@@ -66,6 +66,26 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
                                             at::Tensor invstd, at::Tensor gamma,
                                             bool need_residual_grad);
 
+// SyncBatchNorm passes around the two stats allreduces (syncbn_kernels.hip);
+// x is fp32/fp16/bf16, contiguous or channels_last (4-D/5-D).  weight, bias
+// and the running stats may be undefined.  All on torch's current stream
+// with no host synchronisation.
+// -> fp32 [2C+1] = [sum, sqsum, local per-channel count]
+at::Tensor SyncBnStats(at::Tensor x);
+// stats = allreduced [2C+1]; -> {y, mean, invstd}; updates running stats.
+std::vector<at::Tensor> SyncBnNormalize(at::Tensor x, at::Tensor stats,
+                                        at::Tensor weight, at::Tensor bias,
+                                        at::Tensor running_mean,
+                                        at::Tensor running_var,
+                                        double momentum, double eps);
+// -> fp32 [2C] = [sum(dy), sum(dy * xhat)]
+at::Tensor SyncBnBackwardReduce(at::Tensor x, at::Tensor dy, at::Tensor mean,
+                                at::Tensor invstd);
+// sums = allreduced [2C]; count = 1-element fp32 device tensor (global n).
+at::Tensor SyncBnBackwardApply(at::Tensor x, at::Tensor dy, at::Tensor mean,
+                               at::Tensor invstd, at::Tensor weight,
+                               at::Tensor sums, at::Tensor count);
+
 // Fused SGD step on torch's current stream (one kernel for all buckets;
 // empty `momenta` = plain SGD).  fp32 tensors.
 void FusedSgdStep(std::vector<at::Tensor>& params,

@@ -149,5 +149,45 @@ hipError_t BnBwdApplyLaunch(const void* x, const void* y, const void* dy,
                             const float* sum_gx, long long total, int C,
                             int dt, float inv_count, hipStream_t stream);
 
+// ---- SyncBatchNorm (syncbn_kernels.hip) ------------------------------------
+// Activations are a dense (outer, C, inner) block: planar (N, C, L) tensors
+// pass outer = N, inner = L; channels-last ones pass outer = N*L, inner = 1.
+// dt in {DT_F32, DT_F16, DT_BF16}; every statistic and parameter is fp32.
+// w / b / running_* may be null.  Needs outer * inner < 2^31 (planar) and
+// an element count below 2^24 so the fp32 count word is exact.
+//
+// True when the reductions of this shape go through a kBnBanks * 2 * C
+// float workspace (`banks` below; otherwise it may be null).
+bool SyncBnBanked(long long C, long long inner);
+// out[2C+1] = [sum(C), sqsum(C), outer*inner]; zeroes what it accumulates
+// into, so out (and banks) may come in uninitialised.
+hipError_t SyncBnStatsLaunch(const void* x, long long outer, long long C,
+                             long long inner, int dt, float* banks, float* out,
+                             hipStream_t stream);
+// stats = the allreduced [sum, sqsum, count]; the count is read on device.
+// var clamps at >= 0; running stats use the unbiased n / max(n-1, 1).
+hipError_t SyncBnFinalizeLaunch(const float* stats, float* mean, float* invstd,
+                                float* running_mean, float* running_var,
+                                float momentum, float eps, int C,
+                                hipStream_t stream);
+// y = (x - mean) * invstd * w + b
+hipError_t SyncBnApplyLaunch(const void* x, void* y, const float* mean,
+                             const float* invstd, const float* w,
+                             const float* b, long long outer, long long C,
+                             long long inner, int dt, hipStream_t stream);
+// out[2C] = [sum(dy)(C), sum(dy * xhat)(C)]
+hipError_t SyncBnBwdReduceLaunch(const void* x, const void* dy,
+                                 const float* mean, const float* invstd,
+                                 long long outer, long long C, long long inner,
+                                 int dt, float* banks, float* out,
+                                 hipStream_t stream);
+// dx = w * invstd * (dy - sums[c]/n - xhat * sums[C+c]/n), n = count[0]
+hipError_t SyncBnBwdApplyLaunch(const void* x, const void* dy, void* dx,
+                                const float* mean, const float* invstd,
+                                const float* w, const float* sums,
+                                const float* count, long long outer,
+                                long long C, long long inner, int dt,
+                                hipStream_t stream);
+
 }  // namespace gpu
 }  // namespace hvd
