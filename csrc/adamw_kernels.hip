@@ -13,6 +13,7 @@
 // using denom = sqrt(v)/sqrt(bc2) + eps (torch AdamW definition).
 #include <hip/hip_runtime.h>
 
+#include "grad_scale.h"
 #include "kernels.h"
 
 namespace hvd {
@@ -20,11 +21,15 @@ namespace gpu {
 
 namespace {
 
+template <bool HAS_COEF>
 __global__ __launch_bounds__(256) void fused_adamw_k(
     AdamwBatchArgs args, int blocks_per, float lr, float beta1, float beta2,
-    float eps, float weight_decay, float step_size, float inv_bc2_sqrt) {
+    float eps, float weight_decay, float step_size, float inv_bc2_sqrt,
+    const float* __restrict__ grad_coef) {
   int t = blockIdx.x / blocks_per;
   if (t >= args.count) return;
+  // one uniform load; the gradient tensors are never written
+  const float coef = HAS_COEF ? *grad_coef : 1.0f;
   float* __restrict__ p = (float*)args.params[t];
   const float* __restrict__ g = (const float*)args.grads[t];
   float* __restrict__ m = (float*)args.exp_avg[t];
@@ -51,6 +56,7 @@ __global__ __launch_bounds__(256) void fused_adamw_k(
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float ge = (&gv.x)[k];
+        if (HAS_COEF) ge = scale_grad(ge, coef);
         float me = beta1 * (&mv.x)[k] + (1.0f - beta1) * ge;
         float ve = beta2 * (&vv.x)[k] + (1.0f - beta2) * ge * ge;
         (&mv.x)[k] = me;
@@ -65,6 +71,7 @@ __global__ __launch_bounds__(256) void fused_adamw_k(
   }
   for (long long i = done + tid; i < n; i += nthreads) {
     float ge = g[i];
+    if (HAS_COEF) ge = scale_grad(ge, coef);
     float me = beta1 * m[i] + (1.0f - beta1) * ge;
     float ve = beta2 * v[i] + (1.0f - beta2) * ge * ge;
     m[i] = me;
@@ -78,7 +85,8 @@ __global__ __launch_bounds__(256) void fused_adamw_k(
 
 hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             float beta2, float eps, float weight_decay,
-                            long long step, hipStream_t stream) {
+                            long long step, const float* grad_coef,
+                            hipStream_t stream) {
   if (args.count == 0) return hipSuccess;
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
@@ -86,9 +94,14 @@ hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
   const float inv_bc2_sqrt = 1.0f / sqrtf(bc2);
   const int bpc = 16;
   dim3 grid(args.count * bpc), block(256);
-  fused_adamw_k<<<grid, block, 0, stream>>>(args, bpc, lr, beta1, beta2, eps,
-                                            weight_decay, step_size,
-                                            inv_bc2_sqrt);
+  if (grad_coef)
+    fused_adamw_k<true><<<grid, block, 0, stream>>>(
+        args, bpc, lr, beta1, beta2, eps, weight_decay, step_size,
+        inv_bc2_sqrt, grad_coef);
+  else
+    fused_adamw_k<false><<<grid, block, 0, stream>>>(
+        args, bpc, lr, beta1, beta2, eps, weight_decay, step_size,
+        inv_bc2_sqrt, nullptr);
   return hipGetLastError();
 }
 

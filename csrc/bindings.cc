@@ -130,23 +130,54 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     hvd::gpu::AdasumCombine(a, b);
   });
 
-  // ---- fused optimizer kernels -------------------------------------------
+  // ---- global-norm gradient clipping ------------------------------------
+  m.def("multi_tensor_grad_norm",
+        [](std::vector<at::Tensor> grads, double max_norm) {
+          return hvd::gpu::MultiTensorGradNorm(grads, max_norm);
+        },
+        py::arg("grads"), py::arg("max_norm"));
+  m.def("multi_tensor_scale_",
+        [](std::vector<at::Tensor> tensors, at::Tensor coef) {
+          hvd::gpu::MultiTensorScale(tensors, coef);
+        },
+        py::arg("tensors"), py::arg("coef"));
+
+  // ---- fused optimizer kernels (grad_coef: None or a 1-element fp32
+  // device tensor, e.g. multi_tensor_grad_norm(...)[1:2]) -------------------
+  auto opt_tensor = [](const py::object& o) {
+    return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
+  };
   m.def("fused_sgd_step",
-        [](std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
-           std::vector<at::Tensor> momenta, double lr, double momentum,
-           double weight_decay, double dampening, bool nesterov) {
+        [opt_tensor](std::vector<at::Tensor> params,
+                     std::vector<at::Tensor> grads,
+                     std::vector<at::Tensor> momenta, double lr,
+                     double momentum, double weight_decay, double dampening,
+                     bool nesterov, py::object grad_coef) {
           hvd::gpu::FusedSgdStep(params, grads, momenta, lr, momentum,
-                                 weight_decay, dampening, nesterov);
-        });
+                                 weight_decay, dampening, nesterov,
+                                 opt_tensor(grad_coef));
+        },
+        py::arg("params"), py::arg("grads"), py::arg("momenta"),
+        py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("dampening"), py::arg("nesterov"),
+        py::arg("grad_coef") = py::none());
 
   m.def("fused_adamw_step",
-        [](std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
-           std::vector<at::Tensor> exp_avgs,
-           std::vector<at::Tensor> exp_avg_sqs, double lr, double beta1,
-           double beta2, double eps, double weight_decay, int64_t step) {
+        [opt_tensor](std::vector<at::Tensor> params,
+                     std::vector<at::Tensor> grads,
+                     std::vector<at::Tensor> exp_avgs,
+                     std::vector<at::Tensor> exp_avg_sqs, double lr,
+                     double beta1, double beta2, double eps,
+                     double weight_decay, int64_t step,
+                     py::object grad_coef) {
           hvd::gpu::FusedAdamwStep(params, grads, exp_avgs, exp_avg_sqs, lr,
-                                   beta1, beta2, eps, weight_decay, step);
-        });
+                                   beta1, beta2, eps, weight_decay, step,
+                                   opt_tensor(grad_coef));
+        },
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("step"), py::arg("grad_coef") = py::none());
 
   m.def("fused_bn_relu_forward",
         [](at::Tensor x, py::object residual, at::Tensor gamma, at::Tensor beta,

@@ -86,21 +86,37 @@ at::Tensor SyncBnBackwardApply(at::Tensor x, at::Tensor dy, at::Tensor mean,
                                at::Tensor invstd, at::Tensor weight,
                                at::Tensor sums, at::Tensor count);
 
+// Global-norm clipping (clip_kernels.hip) on torch's current stream with no
+// host synchronisation.  grads: dense fp32/fp16/bf16 tensors of one GPU, any
+// number of them.  -> fp32 [2] = {total_norm, coef}, coef =
+// min(max_norm / (total_norm + 1e-6), 1) as torch.nn.utils.clip_grad_norm_;
+// bitwise reproducible for identical inputs.  An empty list gives norm 0,
+// hence coef 1 by that formula unless max_norm < 1e-6.
+at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
+                               double max_norm);
+// tensors[i] *= coef in place; coef is a 1-element fp32 device tensor.
+void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef);
+
 // Fused SGD step on torch's current stream (one kernel for all buckets;
-// empty `momenta` = plain SGD).  fp32 tensors.
+// empty `momenta` = plain SGD).  fp32 tensors.  grad_coef: undefined, or a
+// 1-element fp32 device tensor the kernel multiplies every gradient element
+// by as it reads it (the gradients are not written).
 void FusedSgdStep(std::vector<at::Tensor>& params,
                   std::vector<at::Tensor>& grads,
                   std::vector<at::Tensor>& momenta, double lr, double momentum,
-                  double weight_decay, double dampening, bool nesterov);
+                  double weight_decay, double dampening, bool nesterov,
+                  at::Tensor grad_coef = at::Tensor());
 
 // Fused AdamW step (decoupled weight decay, torch.optim.AdamW math);
 // step is the 1-based step count for bias correction.  fp32 tensors.
+// grad_coef as in FusedSgdStep.
 void FusedAdamwStep(std::vector<at::Tensor>& params,
                     std::vector<at::Tensor>& grads,
                     std::vector<at::Tensor>& exp_avgs,
                     std::vector<at::Tensor>& exp_avg_sqs, double lr,
                     double beta1, double beta2, double eps,
-                    double weight_decay, int64_t step);
+                    double weight_decay, int64_t step,
+                    at::Tensor grad_coef = at::Tensor());
 
 }  // namespace gpu
 }  // namespace hvd

@@ -93,9 +93,12 @@ struct SgdBatchArgs {
   int count = 0;
 };
 
+// grad_coef: null, or a device fp32 scalar every gradient element is
+// multiplied by (the global-norm clip coefficient) before weight decay and
+// momentum; the gradients themselves are only read.
 hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
                           float weight_decay, float dampening, bool nesterov,
-                          hipStream_t stream);
+                          const float* grad_coef, hipStream_t stream);
 
 // ---- Fused AdamW (adamw_kernels.hip) --------------------------------------
 struct AdamwBatchArgs {
@@ -107,10 +110,44 @@ struct AdamwBatchArgs {
   int count = 0;
 };
 
-// step is 1-based (bias correction uses beta^step).
+// step is 1-based (bias correction uses beta^step).  grad_coef as in
+// FusedSgdLaunch: applied before the moments.
 hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             float beta2, float eps, float weight_decay,
-                            long long step, hipStream_t stream);
+                            long long step, const float* grad_coef,
+                            hipStream_t stream);
+
+// ---- Global-norm gradient clipping (clip_kernels.hip) ----------------------
+// Blocks own fixed kClipChunk-element chunks; block_prefix[t] is the first
+// block of tensor t and block_prefix[count] the grid size, so work is
+// balanced by elements whatever the tensor sizes.  Tensors are dense, of one
+// dtype per launch (dt in {DT_F32, DT_F16, DT_BF16}).
+constexpr long long kClipChunk = 8192;
+
+struct ClipBatchArgs {
+  void* ptr[kCopyBatchCapacity];
+  unsigned long long numel[kCopyBatchCapacity];
+  unsigned int block_prefix[kCopyBatchCapacity + 1] = {0};
+  // first workspace slot of this launch (norm pass only)
+  unsigned long long partial_base = 0;
+  int count = 0;
+};
+
+// Block b of the launch writes sum(x^2) of its chunk (fp32) to
+// partials[args.partial_base + b].
+hipError_t MultiSqNormLaunch(const ClipBatchArgs& args, int dt,
+                             float* partials, hipStream_t stream);
+// Sums partials[0..n) in a fixed order in fp64 (no atomics: bitwise
+// reproducible); out[0] = total_norm = sqrt(sum), out[1] = coef =
+// min(max_norm / (total_norm + 1e-6), 1) with NaN kept (torch's
+// clip_grad_norm_ formula).  n = 0 gives norm 0 and coef min(1e6 * max_norm,
+// 1), i.e. 1 unless max_norm < 1e-6.
+hipError_t ClipFinalizeLaunch(const float* partials, long long n_partials,
+                              float max_norm, float* out, hipStream_t stream);
+// x *= *coef in place; the whole grid returns without touching memory when
+// *coef == 1 (but not when it is NaN).
+hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
+                            const float* coef, hipStream_t stream);
 
 // ---- Fused BatchNorm(+Add)+ReLU (bn_kernels.hip) --------------------------
 // NHWC dense activations [total=N*H*W rows, C channels], C % 8 == 0,

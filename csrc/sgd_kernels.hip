@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "grad_scale.h"
 #include "kernels.h"
 
 namespace hvd {
@@ -14,14 +15,15 @@ namespace gpu {
 
 namespace {
 
-template <bool NESTEROV, bool HAS_MOMENTUM>
-__global__ __launch_bounds__(256) void fused_sgd_k(SgdBatchArgs args,
-                                                   int blocks_per, float lr,
-                                                   float momentum,
-                                                   float weight_decay,
-                                                   float dampening) {
+template <bool NESTEROV, bool HAS_MOMENTUM, bool HAS_COEF>
+__global__ __launch_bounds__(256) void fused_sgd_k(
+    SgdBatchArgs args, int blocks_per, float lr, float momentum,
+    float weight_decay, float dampening,
+    const float* __restrict__ grad_coef) {
   int t = blockIdx.x / blocks_per;
   if (t >= args.count) return;
+  // one uniform load; the gradient tensors are never written
+  const float coef = HAS_COEF ? *grad_coef : 1.0f;
   float* __restrict__ p = (float*)args.params[t];
   const float* __restrict__ g = (const float*)args.grads[t];
   float* __restrict__ m = HAS_MOMENTUM ? (float*)args.momenta[t] : nullptr;
@@ -43,6 +45,7 @@ __global__ __launch_bounds__(256) void fused_sgd_k(SgdBatchArgs args,
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float pe = (&pv.x)[k], ge = (&gv.x)[k];
+        if (HAS_COEF) ge = scale_grad(ge, coef);
         ge += weight_decay * pe;
         if (HAS_MOMENTUM) {
           float me = momentum * (&mv.x)[k] + (1.0f - dampening) * ge;
@@ -57,6 +60,7 @@ __global__ __launch_bounds__(256) void fused_sgd_k(SgdBatchArgs args,
   }
   for (long long i = done + tid; i < n; i += nthreads) {
     float pe = p[i], ge = g[i];
+    if (HAS_COEF) ge = scale_grad(ge, coef);
     ge += weight_decay * pe;
     if (HAS_MOMENTUM) {
       float me = momentum * m[i] + (1.0f - dampening) * ge;
@@ -67,24 +71,36 @@ __global__ __launch_bounds__(256) void fused_sgd_k(SgdBatchArgs args,
   }
 }
 
+template <bool NESTEROV, bool HAS_MOMENTUM>
+void launch_sgd(const SgdBatchArgs& args, float lr, float momentum,
+                float weight_decay, float dampening, const float* grad_coef,
+                hipStream_t stream) {
+  const int bpc = 16;
+  dim3 grid(args.count * bpc), block(256);
+  if (grad_coef)
+    fused_sgd_k<NESTEROV, HAS_MOMENTUM, true><<<grid, block, 0, stream>>>(
+        args, bpc, lr, momentum, weight_decay, dampening, grad_coef);
+  else
+    fused_sgd_k<NESTEROV, HAS_MOMENTUM, false><<<grid, block, 0, stream>>>(
+        args, bpc, lr, momentum, weight_decay, dampening, nullptr);
+}
+
 }  // namespace
 
 hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
                           float weight_decay, float dampening, bool nesterov,
-                          hipStream_t stream) {
+                          const float* grad_coef, hipStream_t stream) {
   if (args.count == 0) return hipSuccess;
-  const int bpc = 16;
-  dim3 grid(args.count * bpc), block(256);
   if (momentum != 0.0f) {
     if (nesterov)
-      fused_sgd_k<true, true><<<grid, block, 0, stream>>>(args, bpc, lr, momentum,
-                                                          weight_decay, dampening);
+      launch_sgd<true, true>(args, lr, momentum, weight_decay, dampening,
+                             grad_coef, stream);
     else
-      fused_sgd_k<false, true><<<grid, block, 0, stream>>>(
-          args, bpc, lr, momentum, weight_decay, dampening);
+      launch_sgd<false, true>(args, lr, momentum, weight_decay, dampening,
+                              grad_coef, stream);
   } else {
-    fused_sgd_k<false, false><<<grid, block, 0, stream>>>(
-        args, bpc, lr, momentum, weight_decay, dampening);
+    launch_sgd<false, false>(args, lr, momentum, weight_decay, dampening,
+                             grad_coef, stream);
   }
   return hipGetLastError();
 }
