@@ -179,6 +179,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("step"), py::arg("grad_coef") = py::none());
 
+  m.def("fused_lamb_step",
+        [opt_tensor](std::vector<at::Tensor> params,
+                     std::vector<at::Tensor> grads,
+                     std::vector<at::Tensor> exp_avgs,
+                     std::vector<at::Tensor> exp_avg_sqs, double lr,
+                     double beta1, double beta2, double eps,
+                     double weight_decay, int64_t step, bool bias_correction,
+                     bool adapt, py::object grad_coef) {
+          return hvd::gpu::FusedLambStep(params, grads, exp_avgs, exp_avg_sqs,
+                                         lr, beta1, beta2, eps, weight_decay,
+                                         step, bias_correction, adapt,
+                                         opt_tensor(grad_coef));
+        },
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("step"), py::arg("bias_correction"), py::arg("adapt"),
+        py::arg("grad_coef") = py::none());
+
   m.def("fused_bn_relu_forward",
         [](at::Tensor x, py::object residual, at::Tensor gamma, at::Tensor beta,
            at::Tensor rm, at::Tensor rv, double momentum, double eps) {

@@ -1700,6 +1700,103 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
   flush();
 }
 
+at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
+                         std::vector<at::Tensor>& grads,
+                         std::vector<at::Tensor>& exp_avgs,
+                         std::vector<at::Tensor>& exp_avg_sqs, double lr,
+                         double beta1, double beta2, double eps,
+                         double weight_decay, int64_t step,
+                         bool bias_correction, bool adapt,
+                         at::Tensor grad_coef) {
+  const size_t n = params.size();
+  if (grads.size() != n || exp_avgs.size() != n || exp_avg_sqs.size() != n)
+    throw std::runtime_error(
+        "horovod_amd: fused_lamb_step needs as many grads, exp_avgs and "
+        "exp_avg_sqs as params");
+  if (step < 1)
+    throw std::runtime_error("horovod_amd: fused_lamb_step: step is 1-based");
+  // validate everything before the first launch: a throw must not leave
+  // half of the parameters updated
+  int device = n == 0 ? (int)c10::hip::current_device() : -1;
+  int64_t total_blocks = 0;
+  bool any_empty = false;
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor* tuple[4] = {&params[i], &grads[i], &exp_avgs[i],
+                                  &exp_avg_sqs[i]};
+    for (const at::Tensor* t : tuple) {
+      if (!t->is_cuda() || t->is_sparse())
+        throw std::runtime_error(
+            "horovod_amd: fused_lamb_step needs dense tensors on one GPU");
+      if (device < 0) device = (int)t->get_device();
+      if (t->get_device() != device)
+        throw std::runtime_error(
+            "horovod_amd: fused_lamb_step needs dense tensors on one GPU");
+      if (t->scalar_type() != at::kFloat)
+        throw std::runtime_error(
+            "horovod_amd: fused_lamb_step supports fp32 tensors only");
+      // the kernels walk memory order, so the four must share one layout
+      const bool same_layout =
+          (t->is_contiguous() && params[i].is_contiguous()) ||
+          (t->sizes() == params[i].sizes() &&
+           t->strides() == params[i].strides());
+      if (!t->is_non_overlapping_and_dense() ||
+          t->numel() != params[i].numel() || !same_layout)
+        throw std::runtime_error(
+            "horovod_amd: fused_lamb_step needs a parameter, its gradient "
+            "and its moments to be dense tensors of one size and layout");
+    }
+    // one tensor too large for a launch's 32-bit block index
+    if (params[i].numel() / kClipChunk >= (int64_t)1 << 30)
+      throw std::runtime_error("horovod_amd: tensor too large for LAMB");
+    total_blocks += (params[i].numel() + kClipChunk - 1) / kClipChunk;
+    any_empty = any_empty || params[i].numel() == 0;
+  }
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  const float* coef = GradCoefPtr(grad_coef, device);
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
+  // sized for the whole call; every slot is written by exactly one block
+  // before the trust kernel of its batch reads it
+  at::Tensor partials =
+      at::empty({std::max<int64_t>(2 * total_blocks, 1)}, f32);
+  // empty tensors take no descriptor: their ratio is the preset 1
+  at::Tensor trust = any_empty ? at::ones({(int64_t)n}, f32)
+                               : at::empty({(int64_t)n}, f32);
+  const LambScalars s =
+      LambFoldScalars((float)lr, (float)beta1, (float)beta2, (float)eps,
+                      (float)weight_decay, step, bias_correction);
+  LambBatchArgs args;
+  unsigned long long base = 0;
+  auto flush = [&] {
+    if (args.count == 0) return;
+    args.partial_base = base;
+    HIP_CHECK(LambMomentsLaunch(args, s, coef, partials.data_ptr<float>(),
+                                stream));
+    HIP_CHECK(LambTrustLaunch(args, partials.data_ptr<float>(), adapt,
+                              trust.data_ptr<float>(), stream));
+    HIP_CHECK(LambUpdateLaunch(args, s, trust.data_ptr<float>(), stream));
+    base += args.block_prefix[args.count];
+    args.count = 0;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    if (params[i].numel() == 0) continue;
+    if (args.count == kCopyBatchCapacity) flush();
+    int64_t blocks = (params[i].numel() + kClipChunk - 1) / kClipChunk;
+    if ((int64_t)args.block_prefix[args.count] + blocks > (int64_t)1 << 30)
+      flush();
+    int k = args.count++;
+    args.params[k] = params[i].data_ptr();
+    args.grads[k] = grads[i].data_ptr();
+    args.exp_avg[k] = exp_avgs[i].data_ptr();
+    args.exp_avg_sq[k] = exp_avg_sqs[i].data_ptr();
+    args.numel[k] = (unsigned long long)params[i].numel();
+    args.out_index[k] = (unsigned int)i;
+    args.block_prefix[k + 1] = args.block_prefix[k] + (unsigned int)blocks;
+  }
+  flush();
+  return trust;
+}
+
 // ---- Fused BN(+Add)+ReLU host side ----------------------------------------
 // Returns {y, save_mean, save_invstd}.  Small per-channel math ([C] tensors)
 // runs through ATen; the big passes are the CDNA4 kernels.

@@ -118,5 +118,23 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
                     double weight_decay, int64_t step,
                     at::Tensor grad_coef = at::Tensor());
 
+// Fused LAMB step (lamb_kernels.hip): AdamW's moments, then per tensor
+// p -= lr * trust * u with u = mhat / (sqrt(vhat) + eps) + weight_decay * p
+// and trust = |p| / |u| when `adapt` and both norms are > 0, else 1.
+// Without bias_correction mhat = m and vhat = v.  Dense fp32 tensors of one
+// GPU, a parameter's four tensors of one size and layout; anything else
+// throws before the first launch.  Three launches per 48 tensors on torch's
+// current stream, no host synchronisation.  -> fp32 [params.size()], the
+// trust ratio applied to each parameter (1 for an empty one); bitwise
+// reproducible for identical inputs.  grad_coef as in FusedSgdStep.
+at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
+                         std::vector<at::Tensor>& grads,
+                         std::vector<at::Tensor>& exp_avgs,
+                         std::vector<at::Tensor>& exp_avg_sqs, double lr,
+                         double beta1, double beta2, double eps,
+                         double weight_decay, int64_t step,
+                         bool bias_correction, bool adapt,
+                         at::Tensor grad_coef = at::Tensor());
+
 }  // namespace gpu
 }  // namespace hvd

@@ -1,5 +1,5 @@
 // Device helper shared by the fused optimizer step kernels
-// (sgd_kernels.hip, adamw_kernels.hip).
+// (sgd_kernels.hip, adamw_kernels.hip, lamb_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -149,6 +149,50 @@ hipError_t ClipFinalizeLaunch(const float* partials, long long n_partials,
 hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
                             const float* coef, hipStream_t stream);
 
+// ---- Fused LAMB (lamb_kernels.hip) -----------------------------------------
+// Three launches per batch, all fp32, work divided into kClipChunk-element
+// chunks like the clip kernels:
+//   1. moments + norms: m, v updated in place, u = mhat / (sqrt(vhat) + eps)
+//      + weight_decay * p formed in registers; block b writes sum(p^2) and
+//      sum(u^2) of its chunk to partials[2 * (partial_base + b) + {0, 1}]
+//   2. trust: one block per tensor sums that tensor's slots in a fixed order
+//      in fp64 (no atomics: bitwise reproducible) and writes
+//      trust[out_index[t]] = |p| / |u| if adapt and both norms are > 0
+//      (false for NaN), else 1
+//   3. update: p -= lr * trust[out_index[t]] * u, u recomputed from m, v
+struct LambBatchArgs {
+  void* params[kCopyBatchCapacity];
+  const void* grads[kCopyBatchCapacity];
+  void* exp_avg[kCopyBatchCapacity];
+  void* exp_avg_sq[kCopyBatchCapacity];
+  unsigned long long numel[kCopyBatchCapacity];
+  unsigned int block_prefix[kCopyBatchCapacity + 1] = {0};
+  // slot of each tensor in the call-wide trust array
+  unsigned int out_index[kCopyBatchCapacity];
+  // first workspace slot pair of this launch
+  unsigned long long partial_base = 0;
+  int count = 0;
+};
+
+// Bias correction folded on the host: mhat = m * inv_bc1, sqrt(vhat) =
+// sqrt(v) * inv_bc2_sqrt (both 1 without bias correction).
+struct LambScalars {
+  float lr, beta1, beta2, eps, weight_decay, inv_bc1, inv_bc2_sqrt;
+};
+
+// step is 1-based.  grad_coef as in FusedSgdLaunch: applied before the
+// moments.
+LambScalars LambFoldScalars(float lr, float beta1, float beta2, float eps,
+                            float weight_decay, long long step,
+                            bool bias_correction);
+hipError_t LambMomentsLaunch(const LambBatchArgs& args, const LambScalars& s,
+                             const float* grad_coef, float* partials,
+                             hipStream_t stream);
+hipError_t LambTrustLaunch(const LambBatchArgs& args, const float* partials,
+                           bool adapt, float* trust, hipStream_t stream);
+hipError_t LambUpdateLaunch(const LambBatchArgs& args, const LambScalars& s,
+                            const float* trust, hipStream_t stream);
+
 // ---- Fused BatchNorm(+Add)+ReLU (bn_kernels.hip) --------------------------
 // NHWC dense activations [total=N*H*W rows, C channels], C % 8 == 0,
 // dt in {DT_F32, DT_F16, DT_BF16}; stats/params fp32.

@@ -5,7 +5,7 @@ One multi-tensor pass computes {total_norm, coef} on the device without a
 host synchronisation; the coefficient is then either applied in place by a
 second multi-tensor kernel (`clip_grad_norm_`) or handed to the fused
 optimizer step, which multiplies the gradient by it as it reads it
-(`FusedSGD` / `FusedAdamW` with `max_grad_norm=`).
+(`FusedSGD` / `FusedAdamW` / `FusedLAMB` with `max_grad_norm=`).
 
 The norm reduces in a fixed order, so identical gradients give a bitwise
 identical coefficient on every data-parallel rank.
