@@ -6,15 +6,13 @@
 // within each tensor, grid = count * blocks_per.
 //
 // Bias correction is folded host-side into step_size = lr/bc1 and
-// inv_bc2_sqrt = 1/sqrt(bc2) so the kernel is pure FMA per element:
-//   m = b1*m + (1-b1)*g
-//   v = b2*v + (1-b2)*g*g
-//   p = p*(1 - lr*wd) - step_size * m / (sqrt(v)*inv_bc2_sqrt... )
-// using denom = sqrt(v)/sqrt(bc2) + eps (torch AdamW definition).
+// inv_bc2_sqrt = 1/sqrt(bc2); the per-element arithmetic is adamw_element
+// in multi_tensor.h (torch AdamW definition, denom = sqrt(v)/sqrt(bc2) +
+// eps).
 #include <hip/hip_runtime.h>
 
-#include "grad_scale.h"
 #include "kernels.h"
+#include "multi_tensor.h"
 
 namespace hvd {
 namespace gpu {
@@ -30,22 +28,18 @@ __global__ __launch_bounds__(256) void fused_adamw_k(
   if (t >= args.count) return;
   // one uniform load; the gradient tensors are never written
   const float coef = HAS_COEF ? *grad_coef : 1.0f;
-  float* __restrict__ p = (float*)args.params[t];
-  const float* __restrict__ g = (const float*)args.grads[t];
-  float* __restrict__ m = (float*)args.exp_avg[t];
-  float* __restrict__ v = (float*)args.exp_avg_sq[t];
+  float* __restrict__ p = (float*)args.ptr[kRowParam][t];
+  const float* __restrict__ g = (const float*)args.ptr[kRowGrad][t];
+  float* __restrict__ m = (float*)args.ptr[kRowExpAvg][t];
+  float* __restrict__ v = (float*)args.ptr[kRowExpAvgSq][t];
   const long long n = (long long)args.numel[t];
   const long long tid =
       (long long)(blockIdx.x % blocks_per) * blockDim.x + threadIdx.x;
   const long long nthreads = (long long)blocks_per * blockDim.x;
   const float decay = 1.0f - lr * weight_decay;
 
-  const bool vec_ok = (((uintptr_t)p & 15) == 0) &&
-                      (((uintptr_t)g & 15) == 0) &&
-                      (((uintptr_t)m & 15) == 0) &&
-                      (((uintptr_t)v & 15) == 0);
   long long done = 0;
-  if (vec_ok) {
+  if (aligned16(p, g, m, v)) {
     const long long nvec = n / 4;
     done = nvec * 4;
     for (long long i = tid; i < nvec; i += nthreads) {
@@ -54,30 +48,18 @@ __global__ __launch_bounds__(256) void fused_adamw_k(
       float4 mv = ((float4*)m)[i];
       float4 vv = ((float4*)v)[i];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float ge = (&gv.x)[k];
-        if (HAS_COEF) ge = scale_grad(ge, coef);
-        float me = beta1 * (&mv.x)[k] + (1.0f - beta1) * ge;
-        float ve = beta2 * (&vv.x)[k] + (1.0f - beta2) * ge * ge;
-        (&mv.x)[k] = me;
-        (&vv.x)[k] = ve;
-        float denom = sqrtf(ve) * inv_bc2_sqrt + eps;
-        (&pv.x)[k] = (&pv.x)[k] * decay - step_size * me / denom;
-      }
+      for (int k = 0; k < 4; ++k)
+        adamw_element<HAS_COEF>((&pv.x)[k], (&gv.x)[k], (&mv.x)[k],
+                                (&vv.x)[k], coef, beta1, beta2, eps, decay,
+                                step_size, inv_bc2_sqrt);
       ((float4*)p)[i] = pv;
       ((float4*)m)[i] = mv;
       ((float4*)v)[i] = vv;
     }
   }
   for (long long i = done + tid; i < n; i += nthreads) {
-    float ge = g[i];
-    if (HAS_COEF) ge = scale_grad(ge, coef);
-    float me = beta1 * m[i] + (1.0f - beta1) * ge;
-    float ve = beta2 * v[i] + (1.0f - beta2) * ge * ge;
-    m[i] = me;
-    v[i] = ve;
-    float denom = sqrtf(ve) * inv_bc2_sqrt + eps;
-    p[i] = p[i] * decay - step_size * me / denom;
+    adamw_element<HAS_COEF>(p[i], g[i], m[i], v[i], coef, beta1, beta2, eps,
+                            decay, step_size, inv_bc2_sqrt);
   }
 }
 
@@ -92,16 +74,12 @@ hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
   const float bc2 = 1.0f - powf(beta2, (float)step);
   const float step_size = lr / bc1;
   const float inv_bc2_sqrt = 1.0f / sqrtf(bc2);
-  const int bpc = 16;
+  const int bpc = kBlocksPerTensor;
   dim3 grid(args.count * bpc), block(256);
-  if (grad_coef)
-    fused_adamw_k<true><<<grid, block, 0, stream>>>(
-        args, bpc, lr, beta1, beta2, eps, weight_decay, step_size,
-        inv_bc2_sqrt, grad_coef);
-  else
-    fused_adamw_k<false><<<grid, block, 0, stream>>>(
-        args, bpc, lr, beta1, beta2, eps, weight_decay, step_size,
-        inv_bc2_sqrt, nullptr);
+  auto kernel = grad_coef ? fused_adamw_k<true> : fused_adamw_k<false>;
+  kernel<<<grid, block, 0, stream>>>(args, bpc, lr, beta1, beta2, eps,
+                                     weight_decay, step_size, inv_bc2_sqrt,
+                                     grad_coef);
   return hipGetLastError();
 }
 

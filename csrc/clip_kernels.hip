@@ -3,7 +3,7 @@
 // and an in-place multi-tensor scale that reads coef from device memory.
 //
 // Work is divided by elements, not by tensor: every block owns one fixed
-// kClipChunk-element chunk of one tensor and finds its tensor by searching
+// kChunkElems-element chunk of one tensor and finds its tensor by searching
 // the per-tensor block prefix in the kernel args, so a 31 M-element embedding
 // gets ~3800 blocks and a 1024-element bias gets one.
 //
@@ -26,22 +26,22 @@ namespace {
 constexpr int kFinalizeThreads = 1024;
 
 template <typename T>
-__global__ __launch_bounds__(kClipThreads) void multi_sqnorm_k(
+__global__ __launch_bounds__(kChunkThreads) void multi_sqnorm_k(
     ClipBatchArgs args, float* __restrict__ partials) {
   const ChunkRef c = find_chunk(args);
-  const T* __restrict__ p = (const T*)args.ptr[c.tensor];
+  const T* __restrict__ p = (const T*)args.ptr[0][c.tensor];
   constexpr int VS = 16 / (int)sizeof(T);
 
   // independent accumulators keep several 16-byte loads in flight
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   long long done = c.begin;
-  // chunk starts are multiples of kClipChunk elements, so the chunk is
+  // chunk starts are multiples of kChunkElems elements, so the chunk is
   // 16-byte aligned exactly when the tensor is
   if (((uintptr_t)p & 15) == 0) {
     const long long nvec = (c.end - c.begin) / VS;
     const uint4* __restrict__ pv = (const uint4*)(p + c.begin);
     done = c.begin + nvec * VS;
-    for (long long i = threadIdx.x; i < nvec; i += kClipThreads) {
+    for (long long i = threadIdx.x; i < nvec; i += kChunkThreads) {
       union {
         uint4 u;
         T e[VS];
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kClipThreads) void multi_sqnorm_k(
       }
     }
   }
-  for (long long i = done + threadIdx.x; i < c.end; i += kClipThreads) {
+  for (long long i = done + threadIdx.x; i < c.end; i += kChunkThreads) {
     float f = (float)p[i];
     acc[0] += f * f;
   }
@@ -90,14 +90,14 @@ __global__ __launch_bounds__(kFinalizeThreads) void clip_finalize_k(
 }
 
 template <typename T>
-__global__ __launch_bounds__(kClipThreads) void multi_scale_k(
+__global__ __launch_bounds__(kChunkThreads) void multi_scale_k(
     ClipBatchArgs args, const float* __restrict__ coef_ptr) {
   const float coef = *coef_ptr;
   // nothing to clip: leave memory untouched (NaN compares unequal and
   // falls through, so a NaN norm still poisons the gradients like torch)
   if (coef == 1.0f) return;
   const ChunkRef c = find_chunk(args);
-  T* __restrict__ p = (T*)args.ptr[c.tensor];
+  T* __restrict__ p = (T*)args.ptr[0][c.tensor];
   constexpr int VS = 16 / (int)sizeof(T);
 
   long long done = c.begin;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kClipThreads) void multi_scale_k(
     const long long nvec = (c.end - c.begin) / VS;
     uint4* __restrict__ pv = (uint4*)(p + c.begin);
     done = c.begin + nvec * VS;
-    for (long long i = threadIdx.x; i < nvec; i += kClipThreads) {
+    for (long long i = threadIdx.x; i < nvec; i += kChunkThreads) {
       union {
         uint4 u;
         T e[VS];
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kClipThreads) void multi_scale_k(
       pv[i] = io.u;
     }
   }
-  for (long long i = done + threadIdx.x; i < c.end; i += kClipThreads)
+  for (long long i = done + threadIdx.x; i < c.end; i += kChunkThreads)
     p[i] = (T)((float)p[i] * coef);
 }
 
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kClipThreads) void multi_scale_k(
 hipError_t MultiSqNormLaunch(const ClipBatchArgs& args, int dt,
                              float* partials, hipStream_t stream) {
   if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
-  dim3 grid(args.block_prefix[args.count]), block(kClipThreads);
+  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
   switch (dt) {
     case DT_F32:
       multi_sqnorm_k<float><<<grid, block, 0, stream>>>(args, partials);
@@ -154,7 +154,7 @@ hipError_t ClipFinalizeLaunch(const float* partials, long long n_partials,
 hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
                             const float* coef, hipStream_t stream) {
   if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
-  dim3 grid(args.block_prefix[args.count]), block(kClipThreads);
+  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
   switch (dt) {
     case DT_F32:
       multi_scale_k<float><<<grid, block, 0, stream>>>(args, coef);

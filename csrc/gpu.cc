@@ -18,6 +18,7 @@
 #include <unordered_map>
 
 #include "core.h"
+#include "hip_check.h"
 #include "kernels.h"
 #include "logging.h"
 #include "timeline.h"
@@ -26,14 +27,6 @@ namespace hvd {
 namespace gpu {
 
 namespace {
-
-#define HIP_CHECK(cmd)                                                      \
-  do {                                                                      \
-    hipError_t e_ = (cmd);                                                  \
-    if (e_ != hipSuccess)                                                   \
-      throw std::runtime_error(std::string("HIP error: ") +                 \
-                               hipGetErrorString(e_) + " at " #cmd);        \
-  } while (0)
 
 #define RCCL_CHECK(cmd)                                                     \
   do {                                                                      \
@@ -1535,266 +1528,6 @@ void AdasumCombine(std::vector<at::Tensor>& a, std::vector<at::Tensor>& b) {
     }
     HIP_CHECK(AdasumScaledAddLaunch(args, dt, dots + start * 3, stream));
   }
-}
-
-namespace {
-
-// Device pointer of an optional clip coefficient: undefined -> null.
-const float* GradCoefPtr(const at::Tensor& coef, int device) {
-  if (!coef.defined()) return nullptr;
-  if (!coef.is_cuda() || coef.get_device() != device ||
-      coef.scalar_type() != at::kFloat || coef.numel() != 1)
-    throw std::runtime_error(
-        "horovod_amd: grad_coef must be a 1-element fp32 tensor on the "
-        "parameters' device");
-  return coef.data_ptr<float>();
-}
-
-int ClipDevice(const at::Tensor& first) {
-  if (!first.is_cuda())
-    throw std::runtime_error(
-        "horovod_amd: clip kernels need dense tensors on one GPU");
-  return (int)first.get_device();
-}
-
-// Dense fp32/fp16/bf16 tensors of one device -> launches of one dtype each,
-// flushed at kCopyBatchCapacity descriptors.  launch(args, dt) gets
-// block_prefix filled in; empty tensors take no descriptor.
-template <typename Launch>
-void ForEachClipBatch(const std::vector<at::Tensor>& tensors, int device,
-                      Launch launch) {
-  static const int kDts[3] = {DT_F32, DT_F16, DT_BF16};
-  ClipBatchArgs args[3];
-  auto flush = [&](int s) {
-    if (args[s].count == 0) return;
-    launch(args[s], kDts[s]);
-    args[s].count = 0;
-  };
-  // validate everything before the first launch: a throw must not leave
-  // half of the tensors scaled
-  for (const auto& t : tensors) {
-    if (!t.is_cuda() || t.get_device() != device || t.is_sparse() ||
-        !t.is_non_overlapping_and_dense())
-      throw std::runtime_error(
-          "horovod_amd: clip kernels need dense tensors on one GPU");
-    if (t.scalar_type() != at::kFloat && t.scalar_type() != at::kHalf &&
-        t.scalar_type() != at::kBFloat16)
-      throw std::runtime_error(
-          "horovod_amd: clip kernels support fp32, fp16 and bf16");
-    // one tensor too large for a launch's 32-bit block index
-    if (t.numel() / kClipChunk >= (int64_t)1 << 30)
-      throw std::runtime_error("horovod_amd: tensor too large to clip");
-  }
-  for (const auto& t : tensors) {
-    int s = t.scalar_type() == at::kFloat ? 0
-            : t.scalar_type() == at::kHalf ? 1 : 2;
-    if (t.numel() == 0) continue;
-    ClipBatchArgs& a = args[s];
-    if (a.count == kCopyBatchCapacity) flush(s);
-    int64_t blocks = (t.numel() + kClipChunk - 1) / kClipChunk;
-    if ((int64_t)a.block_prefix[a.count] + blocks > (int64_t)1 << 30) flush(s);
-    int k = a.count++;
-    a.ptr[k] = t.data_ptr();
-    a.numel[k] = (unsigned long long)t.numel();
-    a.block_prefix[k + 1] = a.block_prefix[k] + (unsigned int)blocks;
-  }
-  for (int s = 0; s < 3; ++s) flush(s);
-}
-
-}  // namespace
-
-at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
-                               double max_norm) {
-  int device = grads.empty() ? (int)c10::hip::current_device()
-                             : ClipDevice(grads[0]);
-  c10::hip::HIPGuard guard(device);
-  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
-  auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
-  int64_t total_blocks = 0;
-  for (const auto& g : grads)
-    total_blocks += (g.numel() + kClipChunk - 1) / kClipChunk;
-  // every slot is written by exactly one block before the finalize reads it
-  at::Tensor partials = at::empty({std::max<int64_t>(total_blocks, 1)}, f32);
-  at::Tensor out = at::empty({2}, f32);
-  unsigned long long base = 0;
-  ForEachClipBatch(grads, device, [&](ClipBatchArgs& args, int dt) {
-    args.partial_base = base;
-    HIP_CHECK(MultiSqNormLaunch(args, dt, partials.data_ptr<float>(), stream));
-    base += args.block_prefix[args.count];
-  });
-  HIP_CHECK(ClipFinalizeLaunch(partials.data_ptr<float>(), (long long)base,
-                               (float)max_norm, out.data_ptr<float>(),
-                               stream));
-  return out;
-}
-
-void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef) {
-  if (tensors.empty()) return;
-  int device = ClipDevice(tensors[0]);
-  c10::hip::HIPGuard guard(device);
-  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
-  const float* c = GradCoefPtr(coef, device);
-  if (!c) throw std::runtime_error("horovod_amd: coef must be defined");
-  ForEachClipBatch(tensors, device, [&](ClipBatchArgs& args, int dt) {
-    HIP_CHECK(MultiScaleLaunch(args, dt, c, stream));
-  });
-}
-
-void FusedSgdStep(std::vector<at::Tensor>& params,
-                  std::vector<at::Tensor>& grads,
-                  std::vector<at::Tensor>& momenta, double lr, double momentum,
-                  double weight_decay, double dampening, bool nesterov,
-                  at::Tensor grad_coef) {
-  if (params.empty()) return;
-  int device = (int)params[0].get_device();
-  c10::hip::HIPGuard guard(device);
-  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
-  const float* coef = GradCoefPtr(grad_coef, device);
-  SgdBatchArgs args;
-  auto flush = [&] {
-    if (args.count == 0) return;
-    HIP_CHECK(FusedSgdLaunch(args, (float)lr, (float)momentum,
-                             (float)weight_decay, (float)dampening, nesterov,
-                             coef, stream));
-    args.count = 0;
-  };
-  for (size_t i = 0; i < params.size(); ++i) {
-    if (args.count == kCopyBatchCapacity) flush();
-    int k = args.count++;
-    args.params[k] = params[i].data_ptr();
-    args.grads[k] = grads[i].data_ptr();
-    args.momenta[k] = momenta.empty() ? nullptr : momenta[i].data_ptr();
-    args.numel[k] = (unsigned long long)params[i].numel();
-  }
-  flush();
-}
-
-void FusedAdamwStep(std::vector<at::Tensor>& params,
-                    std::vector<at::Tensor>& grads,
-                    std::vector<at::Tensor>& exp_avgs,
-                    std::vector<at::Tensor>& exp_avg_sqs, double lr,
-                    double beta1, double beta2, double eps,
-                    double weight_decay, int64_t step, at::Tensor grad_coef) {
-  if (params.empty()) return;
-  int device = (int)params[0].get_device();
-  c10::hip::HIPGuard guard(device);
-  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
-  const float* coef = GradCoefPtr(grad_coef, device);
-  AdamwBatchArgs args;
-  auto flush = [&] {
-    if (args.count == 0) return;
-    HIP_CHECK(FusedAdamwLaunch(args, (float)lr, (float)beta1, (float)beta2,
-                               (float)eps, (float)weight_decay, step, coef,
-                               stream));
-    args.count = 0;
-  };
-  for (size_t i = 0; i < params.size(); ++i) {
-    if (args.count == kCopyBatchCapacity) flush();
-    int k = args.count++;
-    args.params[k] = params[i].data_ptr();
-    args.grads[k] = grads[i].data_ptr();
-    args.exp_avg[k] = exp_avgs[i].data_ptr();
-    args.exp_avg_sq[k] = exp_avg_sqs[i].data_ptr();
-    args.numel[k] = (unsigned long long)params[i].numel();
-  }
-  flush();
-}
-
-at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
-                         std::vector<at::Tensor>& grads,
-                         std::vector<at::Tensor>& exp_avgs,
-                         std::vector<at::Tensor>& exp_avg_sqs, double lr,
-                         double beta1, double beta2, double eps,
-                         double weight_decay, int64_t step,
-                         bool bias_correction, bool adapt,
-                         at::Tensor grad_coef) {
-  const size_t n = params.size();
-  if (grads.size() != n || exp_avgs.size() != n || exp_avg_sqs.size() != n)
-    throw std::runtime_error(
-        "horovod_amd: fused_lamb_step needs as many grads, exp_avgs and "
-        "exp_avg_sqs as params");
-  if (step < 1)
-    throw std::runtime_error("horovod_amd: fused_lamb_step: step is 1-based");
-  // validate everything before the first launch: a throw must not leave
-  // half of the parameters updated
-  int device = n == 0 ? (int)c10::hip::current_device() : -1;
-  int64_t total_blocks = 0;
-  bool any_empty = false;
-  for (size_t i = 0; i < n; ++i) {
-    const at::Tensor* tuple[4] = {&params[i], &grads[i], &exp_avgs[i],
-                                  &exp_avg_sqs[i]};
-    for (const at::Tensor* t : tuple) {
-      if (!t->is_cuda() || t->is_sparse())
-        throw std::runtime_error(
-            "horovod_amd: fused_lamb_step needs dense tensors on one GPU");
-      if (device < 0) device = (int)t->get_device();
-      if (t->get_device() != device)
-        throw std::runtime_error(
-            "horovod_amd: fused_lamb_step needs dense tensors on one GPU");
-      if (t->scalar_type() != at::kFloat)
-        throw std::runtime_error(
-            "horovod_amd: fused_lamb_step supports fp32 tensors only");
-      // the kernels walk memory order, so the four must share one layout
-      const bool same_layout =
-          (t->is_contiguous() && params[i].is_contiguous()) ||
-          (t->sizes() == params[i].sizes() &&
-           t->strides() == params[i].strides());
-      if (!t->is_non_overlapping_and_dense() ||
-          t->numel() != params[i].numel() || !same_layout)
-        throw std::runtime_error(
-            "horovod_amd: fused_lamb_step needs a parameter, its gradient "
-            "and its moments to be dense tensors of one size and layout");
-    }
-    // one tensor too large for a launch's 32-bit block index
-    if (params[i].numel() / kClipChunk >= (int64_t)1 << 30)
-      throw std::runtime_error("horovod_amd: tensor too large for LAMB");
-    total_blocks += (params[i].numel() + kClipChunk - 1) / kClipChunk;
-    any_empty = any_empty || params[i].numel() == 0;
-  }
-  c10::hip::HIPGuard guard(device);
-  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
-  const float* coef = GradCoefPtr(grad_coef, device);
-  auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
-  // sized for the whole call; every slot is written by exactly one block
-  // before the trust kernel of its batch reads it
-  at::Tensor partials =
-      at::empty({std::max<int64_t>(2 * total_blocks, 1)}, f32);
-  // empty tensors take no descriptor: their ratio is the preset 1
-  at::Tensor trust = any_empty ? at::ones({(int64_t)n}, f32)
-                               : at::empty({(int64_t)n}, f32);
-  const LambScalars s =
-      LambFoldScalars((float)lr, (float)beta1, (float)beta2, (float)eps,
-                      (float)weight_decay, step, bias_correction);
-  LambBatchArgs args;
-  unsigned long long base = 0;
-  auto flush = [&] {
-    if (args.count == 0) return;
-    args.partial_base = base;
-    HIP_CHECK(LambMomentsLaunch(args, s, coef, partials.data_ptr<float>(),
-                                stream));
-    HIP_CHECK(LambTrustLaunch(args, partials.data_ptr<float>(), adapt,
-                              trust.data_ptr<float>(), stream));
-    HIP_CHECK(LambUpdateLaunch(args, s, trust.data_ptr<float>(), stream));
-    base += args.block_prefix[args.count];
-    args.count = 0;
-  };
-  for (size_t i = 0; i < n; ++i) {
-    if (params[i].numel() == 0) continue;
-    if (args.count == kCopyBatchCapacity) flush();
-    int64_t blocks = (params[i].numel() + kClipChunk - 1) / kClipChunk;
-    if ((int64_t)args.block_prefix[args.count] + blocks > (int64_t)1 << 30)
-      flush();
-    int k = args.count++;
-    args.params[k] = params[i].data_ptr();
-    args.grads[k] = grads[i].data_ptr();
-    args.exp_avg[k] = exp_avgs[i].data_ptr();
-    args.exp_avg_sq[k] = exp_avg_sqs[i].data_ptr();
-    args.numel[k] = (unsigned long long)params[i].numel();
-    args.out_index[k] = (unsigned int)i;
-    args.block_prefix[k + 1] = args.block_prefix[k] + (unsigned int)blocks;
-  }
-  flush();
-  return trust;
 }
 
 // ---- Fused BN(+Add)+ReLU host side ----------------------------------------

@@ -86,6 +86,7 @@ at::Tensor SyncBnBackwardApply(at::Tensor x, at::Tensor dy, at::Tensor mean,
                                at::Tensor invstd, at::Tensor weight,
                                at::Tensor sums, at::Tensor count);
 
+// ---- Multi-tensor kernels; defined in multi_tensor.cc ----------------------
 // Global-norm clipping (clip_kernels.hip) on torch's current stream with no
 // host synchronisation.  grads: dense fp32/fp16/bf16 tensors of one GPU, any
 // number of them.  -> fp32 [2] = {total_norm, coef}, coef =
@@ -97,8 +98,12 @@ at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
 // tensors[i] *= coef in place; coef is a 1-element fp32 device tensor.
 void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef);
 
-// Fused SGD step on torch's current stream (one kernel for all buckets;
-// empty `momenta` = plain SGD).  fp32 tensors.  grad_coef: undefined, or a
+// The three steps below take dense fp32 tensors of one GPU, lists of one
+// length, a parameter's tensors of one size and layout; anything else throws
+// before the first launch.  An empty tensor is skipped.
+//
+// Fused SGD step on torch's current stream (one launch per 48 tensors;
+// `momenta` is read only when momentum != 0).  grad_coef: undefined, or a
 // 1-element fp32 device tensor the kernel multiplies every gradient element
 // by as it reads it (the gradients are not written).
 void FusedSgdStep(std::vector<at::Tensor>& params,
@@ -108,8 +113,8 @@ void FusedSgdStep(std::vector<at::Tensor>& params,
                   at::Tensor grad_coef = at::Tensor());
 
 // Fused AdamW step (decoupled weight decay, torch.optim.AdamW math);
-// step is the 1-based step count for bias correction.  fp32 tensors.
-// grad_coef as in FusedSgdStep.
+// step is the 1-based step count for bias correction.  grad_coef as in
+// FusedSgdStep.
 void FusedAdamwStep(std::vector<at::Tensor>& params,
                     std::vector<at::Tensor>& grads,
                     std::vector<at::Tensor>& exp_avgs,
@@ -121,12 +126,11 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
 // Fused LAMB step (lamb_kernels.hip): AdamW's moments, then per tensor
 // p -= lr * trust * u with u = mhat / (sqrt(vhat) + eps) + weight_decay * p
 // and trust = |p| / |u| when `adapt` and both norms are > 0, else 1.
-// Without bias_correction mhat = m and vhat = v.  Dense fp32 tensors of one
-// GPU, a parameter's four tensors of one size and layout; anything else
-// throws before the first launch.  Three launches per 48 tensors on torch's
-// current stream, no host synchronisation.  -> fp32 [params.size()], the
-// trust ratio applied to each parameter (1 for an empty one); bitwise
-// reproducible for identical inputs.  grad_coef as in FusedSgdStep.
+// Without bias_correction mhat = m and vhat = v.  Three launches per 48
+// tensors on torch's current stream, no host synchronisation.  -> fp32
+// [params.size()], the trust ratio applied to each parameter (1 for an empty
+// one); bitwise reproducible for identical inputs.  grad_coef as in
+// FusedSgdStep.
 at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                          std::vector<at::Tensor>& grads,
                          std::vector<at::Tensor>& exp_avgs,

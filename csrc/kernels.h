@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace hvd {
 namespace gpu {
 
@@ -84,15 +86,62 @@ hipError_t AdasumDotsLaunch(const AdasumBatchArgs& args, int dt, double* dots,
 hipError_t AdasumScaledAddLaunch(const AdasumBatchArgs& args, int dt,
                                  const double* dots, hipStream_t stream);
 
-// ---- Fused SGD (sgd_kernels.hip) ------------------------------------------
-struct SgdBatchArgs {
-  void* params[kCopyBatchCapacity];
-  const void* grads[kCopyBatchCapacity];
-  void* momenta[kCopyBatchCapacity];
+// ---- Multi-tensor kernels: clip, fused SGD / AdamW / LAMB ------------------
+// All take one by-value descriptor batch of at most kCopyBatchCapacity dense
+// tensors, filled by multi_tensor.cc: ROWS rows of device pointers (tensor t
+// is ptr[row][t]) and the element counts.  SGD and AdamW give every
+// descriptor a fixed number of blocks.  The CHUNKED kernels (clip, LAMB) give
+// every block one kChunkElems-element chunk of one tensor: block_prefix[t] is
+// the first block of tensor t and block_prefix[count] the grid size, so work
+// is balanced by elements whatever the tensor sizes.
+constexpr long long kChunkElems = 8192;
+
+inline long long ChunkBlocks(long long numel) {
+  return (numel + kChunkElems - 1) / kChunkElems;
+}
+
+struct ChunkFields {
+  unsigned int block_prefix[kCopyBatchCapacity + 1] = {0};
+  // first workspace slot of this launch: block b reduces into slot
+  // partial_base + b (a pair of floats for LAMB)
+  unsigned long long partial_base = 0;
+};
+struct IndexFields {
+  // slot of each tensor in a call-wide per-tensor output (LAMB's trust array)
+  unsigned int out_index[kCopyBatchCapacity];
+};
+template <int> struct NoFields {};
+
+template <int ROWS, bool CHUNKED, bool INDEXED = false>
+struct MultiTensorArgs
+    : std::conditional<CHUNKED, ChunkFields, NoFields<0>>::type,
+      std::conditional<INDEXED, IndexFields, NoFields<1>>::type {
+  static constexpr int kRows = ROWS;
+  static constexpr bool kChunked = CHUNKED;
+  static constexpr bool kIndexed = INDEXED;
+  void* ptr[ROWS][kCopyBatchCapacity];
   unsigned long long numel[kCopyBatchCapacity];
   int count = 0;
 };
 
+// Pointer rows.  Gradients are only ever read.
+enum MultiTensorRow {
+  kRowParam = 0,
+  kRowGrad = 1,
+  kRowMomentum = 2,  // SGD; null when momentum == 0
+  kRowExpAvg = 2,    // AdamW, LAMB
+  kRowExpAvgSq = 3,
+};
+
+using ClipBatchArgs = MultiTensorArgs<1, true>;
+using SgdBatchArgs = MultiTensorArgs<3, false>;
+using AdamwBatchArgs = MultiTensorArgs<4, false>;
+using LambBatchArgs = MultiTensorArgs<4, true, true>;
+static_assert(sizeof(ClipBatchArgs) == 984 && sizeof(SgdBatchArgs) == 1544 &&
+                  sizeof(AdamwBatchArgs) == 1928 && sizeof(LambBatchArgs) == 2328,
+              "kernarg bytes of the four structs these replaced");
+
+// ---- Fused SGD (sgd_kernels.hip) ------------------------------------------
 // grad_coef: null, or a device fp32 scalar every gradient element is
 // multiplied by (the global-norm clip coefficient) before weight decay and
 // momentum; the gradients themselves are only read.
@@ -101,15 +150,6 @@ hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
                           const float* grad_coef, hipStream_t stream);
 
 // ---- Fused AdamW (adamw_kernels.hip) --------------------------------------
-struct AdamwBatchArgs {
-  void* params[kCopyBatchCapacity];
-  const void* grads[kCopyBatchCapacity];
-  void* exp_avg[kCopyBatchCapacity];
-  void* exp_avg_sq[kCopyBatchCapacity];
-  unsigned long long numel[kCopyBatchCapacity];
-  int count = 0;
-};
-
 // step is 1-based (bias correction uses beta^step).  grad_coef as in
 // FusedSgdLaunch: applied before the moments.
 hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
@@ -118,21 +158,9 @@ hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             hipStream_t stream);
 
 // ---- Global-norm gradient clipping (clip_kernels.hip) ----------------------
-// Blocks own fixed kClipChunk-element chunks; block_prefix[t] is the first
-// block of tensor t and block_prefix[count] the grid size, so work is
-// balanced by elements whatever the tensor sizes.  Tensors are dense, of one
-// dtype per launch (dt in {DT_F32, DT_F16, DT_BF16}).
-constexpr long long kClipChunk = 8192;
-
-struct ClipBatchArgs {
-  void* ptr[kCopyBatchCapacity];
-  unsigned long long numel[kCopyBatchCapacity];
-  unsigned int block_prefix[kCopyBatchCapacity + 1] = {0};
-  // first workspace slot of this launch (norm pass only)
-  unsigned long long partial_base = 0;
-  int count = 0;
-};
-
+// Chunked.  One row; tensors are dense, of one dtype per launch (dt in
+// {DT_F32, DT_F16, DT_BF16}).
+//
 // Block b of the launch writes sum(x^2) of its chunk (fp32) to
 // partials[args.partial_base + b].
 hipError_t MultiSqNormLaunch(const ClipBatchArgs& args, int dt,
@@ -150,8 +178,7 @@ hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
                             const float* coef, hipStream_t stream);
 
 // ---- Fused LAMB (lamb_kernels.hip) -----------------------------------------
-// Three launches per batch, all fp32, work divided into kClipChunk-element
-// chunks like the clip kernels:
+// Chunked.  Three launches per batch, all fp32:
 //   1. moments + norms: m, v updated in place, u = mhat / (sqrt(vhat) + eps)
 //      + weight_decay * p formed in registers; block b writes sum(p^2) and
 //      sum(u^2) of its chunk to partials[2 * (partial_base + b) + {0, 1}]
@@ -160,19 +187,6 @@ hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
 //      trust[out_index[t]] = |p| / |u| if adapt and both norms are > 0
 //      (false for NaN), else 1
 //   3. update: p -= lr * trust[out_index[t]] * u, u recomputed from m, v
-struct LambBatchArgs {
-  void* params[kCopyBatchCapacity];
-  const void* grads[kCopyBatchCapacity];
-  void* exp_avg[kCopyBatchCapacity];
-  void* exp_avg_sq[kCopyBatchCapacity];
-  unsigned long long numel[kCopyBatchCapacity];
-  unsigned int block_prefix[kCopyBatchCapacity + 1] = {0};
-  // slot of each tensor in the call-wide trust array
-  unsigned int out_index[kCopyBatchCapacity];
-  // first workspace slot pair of this launch
-  unsigned long long partial_base = 0;
-  int count = 0;
-};
 
 // Bias correction folded on the host: mhat = m * inv_bc1, sqrt(vhat) =
 // sqrt(v) * inv_bc2_sqrt (both 1 without bias correction).

@@ -12,7 +12,7 @@
 //                       and no model-sized temporary)
 //
 // Work is divided like the clip kernels: every block of 1. and 3. owns one
-// kClipChunk-element chunk of one tensor (multi_tensor.h).  There are no
+// kChunkElems-element chunk of one tensor (multi_tensor.h).  There are no
 // atomics and every sum runs in a fixed order, so identical inputs give
 // bitwise identical trust ratios: data-parallel ranks hold replicated
 // parameters and averaged gradients and must derive the same ratios without
@@ -24,7 +24,6 @@
 
 #include <cmath>
 
-#include "grad_scale.h"
 #include "kernels.h"
 #include "multi_tensor.h"
 
@@ -35,73 +34,47 @@ namespace {
 
 constexpr int kTrustThreads = 256;
 
-// u of the definition from the already-updated moments.
-__device__ __forceinline__ float lamb_u(float p, float m, float v,
-                                        const LambScalars& s) {
-  const float denom = sqrtf(v) * s.inv_bc2_sqrt + s.eps;
-  return (m * s.inv_bc1) / denom + s.weight_decay * p;
-}
-
 template <bool HAS_COEF>
-__global__ __launch_bounds__(kClipThreads) void lamb_moments_k(
+__global__ __launch_bounds__(kChunkThreads) void lamb_moments_k(
     LambBatchArgs args, LambScalars s, const float* __restrict__ grad_coef,
     float* __restrict__ partials) {
   const ChunkRef c = find_chunk(args);
   // one uniform load; the gradient tensors are never written
   const float coef = HAS_COEF ? *grad_coef : 1.0f;
-  const float* __restrict__ p = (const float*)args.params[c.tensor];
-  const float* __restrict__ g = (const float*)args.grads[c.tensor];
-  float* __restrict__ m = (float*)args.exp_avg[c.tensor];
-  float* __restrict__ v = (float*)args.exp_avg_sq[c.tensor];
+  const float* __restrict__ p = (const float*)args.ptr[kRowParam][c.tensor];
+  const float* __restrict__ g = (const float*)args.ptr[kRowGrad][c.tensor];
+  float* __restrict__ m = (float*)args.ptr[kRowExpAvg][c.tensor];
+  float* __restrict__ v = (float*)args.ptr[kRowExpAvgSq][c.tensor];
 
   // independent accumulators, one per lane of the 16-byte vector
   float pp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float uu[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   long long done = c.begin;
-  // chunk starts are multiples of kClipChunk elements, so the chunk is
+  // chunk starts are multiples of kChunkElems elements, so the chunk is
   // 16-byte aligned exactly when the tensor is
-  const bool vec_ok = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) |
-                        ((uintptr_t)v)) & 15) == 0;
-  if (vec_ok) {
+  if (aligned16(p, g, m, v)) {
     const long long nvec = (c.end - c.begin) / 4;
     const float4* __restrict__ p4 = (const float4*)(p + c.begin);
     const float4* __restrict__ g4 = (const float4*)(g + c.begin);
     float4* __restrict__ m4 = (float4*)(m + c.begin);
     float4* __restrict__ v4 = (float4*)(v + c.begin);
     done = c.begin + nvec * 4;
-    for (long long i = threadIdx.x; i < nvec; i += kClipThreads) {
+    for (long long i = threadIdx.x; i < nvec; i += kChunkThreads) {
       const float4 pv = p4[i];
       const float4 gv = g4[i];
       float4 mv = m4[i];
       float4 vv = v4[i];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float ge = (&gv.x)[k];
-        if (HAS_COEF) ge = scale_grad(ge, coef);
-        const float pe = (&pv.x)[k];
-        const float me = s.beta1 * (&mv.x)[k] + (1.0f - s.beta1) * ge;
-        const float ve = s.beta2 * (&vv.x)[k] + (1.0f - s.beta2) * ge * ge;
-        (&mv.x)[k] = me;
-        (&vv.x)[k] = ve;
-        const float u = lamb_u(pe, me, ve, s);
-        pp[k] += pe * pe;
-        uu[k] += u * u;
-      }
+      for (int k = 0; k < 4; ++k)
+        lamb_moments_element<HAS_COEF>((&pv.x)[k], (&gv.x)[k], (&mv.x)[k],
+                                       (&vv.x)[k], coef, s, pp[k], uu[k]);
       m4[i] = mv;
       v4[i] = vv;
     }
   }
-  for (long long i = done + threadIdx.x; i < c.end; i += kClipThreads) {
-    float ge = g[i];
-    if (HAS_COEF) ge = scale_grad(ge, coef);
-    const float pe = p[i];
-    const float me = s.beta1 * m[i] + (1.0f - s.beta1) * ge;
-    const float ve = s.beta2 * v[i] + (1.0f - s.beta2) * ge * ge;
-    m[i] = me;
-    v[i] = ve;
-    const float u = lamb_u(pe, me, ve, s);
-    pp[0] += pe * pe;
-    uu[0] += u * u;
+  for (long long i = done + threadIdx.x; i < c.end; i += kChunkThreads) {
+    lamb_moments_element<HAS_COEF>(p[i], g[i], m[i], v[i], coef, s, pp[0],
+                                   uu[0]);
   }
   const float pp_total = block_sum((pp[0] + pp[1]) + (pp[2] + pp[3]));
   // block_sum's LDS is shared by both calls: thread 0 must be done reading
@@ -151,38 +124,35 @@ __global__ __launch_bounds__(kTrustThreads) void lamb_trust_k(
   }
 }
 
-__global__ __launch_bounds__(kClipThreads) void lamb_update_k(
+__global__ __launch_bounds__(kChunkThreads) void lamb_update_k(
     LambBatchArgs args, LambScalars s, const float* __restrict__ trust) {
   const ChunkRef c = find_chunk(args);
   const float step = s.lr * trust[args.out_index[c.tensor]];
-  float* __restrict__ p = (float*)args.params[c.tensor];
-  const float* __restrict__ m = (const float*)args.exp_avg[c.tensor];
-  const float* __restrict__ v = (const float*)args.exp_avg_sq[c.tensor];
+  float* __restrict__ p = (float*)args.ptr[kRowParam][c.tensor];
+  const float* __restrict__ m = (const float*)args.ptr[kRowExpAvg][c.tensor];
+  const float* __restrict__ v = (const float*)args.ptr[kRowExpAvgSq][c.tensor];
 
   long long done = c.begin;
-  const bool vec_ok =
-      ((((uintptr_t)p) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
-  if (vec_ok) {
+  if (aligned16(p, m, v)) {
     const long long nvec = (c.end - c.begin) / 4;
     float4* __restrict__ p4 = (float4*)(p + c.begin);
     const float4* __restrict__ m4 = (const float4*)(m + c.begin);
     const float4* __restrict__ v4 = (const float4*)(v + c.begin);
     done = c.begin + nvec * 4;
-    for (long long i = threadIdx.x; i < nvec; i += kClipThreads) {
+    for (long long i = threadIdx.x; i < nvec; i += kChunkThreads) {
       float4 pv = p4[i];
       const float4 mv = m4[i];
       const float4 vv = v4[i];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float pe = (&pv.x)[k];
-        (&pv.x)[k] = pe - step * lamb_u(pe, (&mv.x)[k], (&vv.x)[k], s);
-      }
+      for (int k = 0; k < 4; ++k)
+        lamb_update_element((&pv.x)[k], (&mv.x)[k], (&vv.x)[k], step, s);
       p4[i] = pv;
     }
   }
-  for (long long i = done + threadIdx.x; i < c.end; i += kClipThreads) {
-    const float pe = p[i];
-    p[i] = pe - step * lamb_u(pe, m[i], v[i], s);
+  for (long long i = done + threadIdx.x; i < c.end; i += kChunkThreads) {
+    float pe = p[i];
+    lamb_update_element(pe, m[i], v[i], step, s);
+    p[i] = pe;
   }
 }
 
@@ -212,13 +182,9 @@ hipError_t LambMomentsLaunch(const LambBatchArgs& args, const LambScalars& s,
                              const float* grad_coef, float* partials,
                              hipStream_t stream) {
   if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
-  dim3 grid(args.block_prefix[args.count]), block(kClipThreads);
-  if (grad_coef)
-    lamb_moments_k<true><<<grid, block, 0, stream>>>(args, s, grad_coef,
-                                                     partials);
-  else
-    lamb_moments_k<false><<<grid, block, 0, stream>>>(args, s, nullptr,
-                                                      partials);
+  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
+  auto kernel = grad_coef ? lamb_moments_k<true> : lamb_moments_k<false>;
+  kernel<<<grid, block, 0, stream>>>(args, s, grad_coef, partials);
   return hipGetLastError();
 }
 
@@ -233,7 +199,7 @@ hipError_t LambTrustLaunch(const LambBatchArgs& args, const float* partials,
 hipError_t LambUpdateLaunch(const LambBatchArgs& args, const LambScalars& s,
                             const float* trust, hipStream_t stream) {
   if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
-  dim3 grid(args.block_prefix[args.count]), block(kClipThreads);
+  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
   lamb_update_k<<<grid, block, 0, stream>>>(args, s, trust);
   return hipGetLastError();
 }

@@ -1,0 +1,291 @@
+// Host side of the multi-tensor kernels: global-norm clipping
+// (clip_kernels.hip) and the fused SGD / AdamW / LAMB steps
+// (sgd_kernels.hip, adamw_kernels.hip, lamb_kernels.hip), declared in gpu.h.
+// Every entry point validates all of its tensors before the first launch (a
+// throw must not leave half of them updated), then fills descriptor batches
+// (MultiTensorArgs, kernels.h) through a Batcher, on torch's current stream.
+#include "gpu.h"
+
+#include <c10/hip/HIPGuard.h>
+#include <c10/hip/HIPStream.h>
+
+#include <algorithm>
+#include <functional>
+#include <string>
+
+#include "hip_check.h"
+#include "kernels.h"
+
+namespace hvd {
+namespace gpu {
+
+namespace {
+
+using TensorList = std::vector<at::Tensor>;
+// Parallel lists: tensor i of list r goes to pointer row r of a descriptor.
+using Rows = std::vector<const TensorList*>;
+
+// Device pointer of an optional clip coefficient: undefined -> null.
+const float* GradCoefPtr(const at::Tensor& coef, int device) {
+  if (!coef.defined()) return nullptr;
+  if (!coef.is_cuda() || coef.get_device() != device ||
+      coef.scalar_type() != at::kFloat || coef.numel() != 1)
+    throw std::runtime_error(
+        "horovod_amd: grad_coef must be a 1-element fp32 tensor on the "
+        "parameters' device");
+  return coef.data_ptr<float>();
+}
+
+struct TupleInfo {
+  int device;            // of every tensor (the current one without tensors)
+  int64_t chunk_blocks;  // sum of ChunkBlocks over the tuples
+  bool any_empty;
+};
+
+// What the optimizer kernels need of the tuples (rows[0][i], rows[1][i], ...),
+// rows[0] being the parameters and `others` naming the rest: lists of one
+// length, dense fp32 tensors on one GPU, each tuple of one size and layout
+// (the kernels walk memory order), and for `chunked` kernels the size limit.
+TupleInfo CheckTuples(const std::string& op, const char* others,
+                      const Rows& rows, bool chunked) {
+  auto fail = [&op](const std::string& what) {
+    throw std::runtime_error("horovod_amd: " + op + what);
+  };
+  const TensorList& params = *rows[0];
+  const size_t n = params.size();
+  for (const TensorList* list : rows)
+    if (list->size() != n)
+      fail(std::string(" needs as many ") + others + " as params");
+  TupleInfo info{n == 0 ? (int)c10::hip::current_device() : -1, 0, false};
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor& p = params[i];
+    for (const TensorList* list : rows) {
+      const at::Tensor& t = (*list)[i];
+      if (info.device < 0 && t.is_cuda()) info.device = (int)t.get_device();
+      if (!t.is_cuda() || t.is_sparse() || t.get_device() != info.device)
+        fail(" needs dense tensors on one GPU");
+      if (t.scalar_type() != at::kFloat) fail(" supports fp32 tensors only");
+      const bool same_layout =
+          (t.is_contiguous() && p.is_contiguous()) ||
+          (t.sizes() == p.sizes() && t.strides() == p.strides());
+      if (!t.is_non_overlapping_and_dense() || t.numel() != p.numel() ||
+          !same_layout)
+        fail(" needs a parameter, its gradient and its moments to be dense "
+             "tensors of one size and layout");
+    }
+    // one tensor too large for a launch's 32-bit block index
+    if (chunked && p.numel() / kChunkElems >= (int64_t)1 << 30)
+      fail(": tensor too large");
+    info.chunk_blocks += ChunkBlocks(p.numel());
+    info.any_empty = info.any_empty || p.numel() == 0;
+  }
+  return info;
+}
+
+// Fills descriptors one tensor tuple at a time and hands every batch to
+// `launch`: when it is full, when a chunked one would pass 2^30 blocks, and
+// at the final Flush().  Empty tensors take no descriptor.
+template <typename Args>
+class Batcher {
+ public:
+  explicit Batcher(std::function<void(Args&)> launch)
+      : launch_(std::move(launch)) {}
+
+  // Tuple i of `rows`; `index`: its slot in an indexed per-tensor output.
+  void Add(const Rows& rows, size_t i, unsigned int index = 0) {
+    const int64_t numel = (*rows[0])[i].numel();
+    if (numel == 0) return;
+    if (args_.count == kCopyBatchCapacity) Flush();
+    const int64_t blocks = ChunkBlocks(numel);
+    if constexpr (Args::kChunked) {
+      if ((int64_t)args_.block_prefix[args_.count] + blocks > (int64_t)1 << 30)
+        Flush();
+    }
+    const int k = args_.count++;
+    for (size_t r = 0; r < (size_t)Args::kRows; ++r)
+      args_.ptr[r][k] = r < rows.size() ? (*rows[r])[i].data_ptr() : nullptr;
+    args_.numel[k] = (unsigned long long)numel;
+    if constexpr (Args::kChunked)
+      args_.block_prefix[k + 1] = args_.block_prefix[k] + (unsigned int)blocks;
+    if constexpr (Args::kIndexed) args_.out_index[k] = index;
+  }
+
+  void Flush() {
+    if (args_.count == 0) return;
+    launch_(args_);
+    args_.count = 0;
+  }
+
+ private:
+  Args args_;
+  std::function<void(Args&)> launch_;
+};
+
+int ClipDevice(const at::Tensor& first) {
+  if (!first.is_cuda())
+    throw std::runtime_error(
+        "horovod_amd: clip kernels need dense tensors on one GPU");
+  return (int)first.get_device();
+}
+
+// Dense fp32/fp16/bf16 tensors of one device -> launches of one dtype each.
+// launch(args, dt) gets block_prefix filled in.
+void ForEachClipBatch(const TensorList& tensors, int device,
+                      const std::function<void(ClipBatchArgs&, int)>& launch) {
+  for (const auto& t : tensors) {
+    if (!t.is_cuda() || t.get_device() != device || t.is_sparse() ||
+        !t.is_non_overlapping_and_dense())
+      throw std::runtime_error(
+          "horovod_amd: clip kernels need dense tensors on one GPU");
+    if (t.scalar_type() != at::kFloat && t.scalar_type() != at::kHalf &&
+        t.scalar_type() != at::kBFloat16)
+      throw std::runtime_error(
+          "horovod_amd: clip kernels support fp32, fp16 and bf16");
+    // one tensor too large for a launch's 32-bit block index
+    if (t.numel() / kChunkElems >= (int64_t)1 << 30)
+      throw std::runtime_error("horovod_amd: tensor too large to clip");
+  }
+  auto of = [&launch](int dt) {
+    return Batcher<ClipBatchArgs>(
+        [&launch, dt](ClipBatchArgs& args) { launch(args, dt); });
+  };
+  Batcher<ClipBatchArgs> batch[3] = {of(DT_F32), of(DT_F16), of(DT_BF16)};
+  const Rows rows{&tensors};
+  for (size_t i = 0; i < tensors.size(); ++i) {
+    const auto dt = tensors[i].scalar_type();
+    batch[dt == at::kFloat ? 0 : dt == at::kHalf ? 1 : 2].Add(rows, i);
+  }
+  for (auto& b : batch) b.Flush();
+}
+
+}  // namespace
+
+at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
+                               double max_norm) {
+  int device = grads.empty() ? (int)c10::hip::current_device()
+                             : ClipDevice(grads[0]);
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
+  int64_t total_blocks = 0;
+  for (const auto& g : grads) total_blocks += ChunkBlocks(g.numel());
+  // every slot is written by exactly one block before the finalize reads it
+  at::Tensor partials = at::empty({std::max<int64_t>(total_blocks, 1)}, f32);
+  at::Tensor out = at::empty({2}, f32);
+  unsigned long long base = 0;
+  ForEachClipBatch(grads, device, [&](ClipBatchArgs& args, int dt) {
+    args.partial_base = base;
+    HIP_CHECK(MultiSqNormLaunch(args, dt, partials.data_ptr<float>(), stream));
+    base += args.block_prefix[args.count];
+  });
+  HIP_CHECK(ClipFinalizeLaunch(partials.data_ptr<float>(), (long long)base,
+                               (float)max_norm, out.data_ptr<float>(),
+                               stream));
+  return out;
+}
+
+void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef) {
+  if (tensors.empty()) return;
+  int device = ClipDevice(tensors[0]);
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  const float* c = GradCoefPtr(coef, device);
+  if (!c) throw std::runtime_error("horovod_amd: coef must be defined");
+  ForEachClipBatch(tensors, device, [&](ClipBatchArgs& args, int dt) {
+    HIP_CHECK(MultiScaleLaunch(args, dt, c, stream));
+  });
+}
+
+void FusedSgdStep(std::vector<at::Tensor>& params,
+                  std::vector<at::Tensor>& grads,
+                  std::vector<at::Tensor>& momenta, double lr, double momentum,
+                  double weight_decay, double dampening, bool nesterov,
+                  at::Tensor grad_coef) {
+  // the kernel reads the momentum row exactly when the launcher sees a
+  // nonzero fp32 momentum; without it `momenta` is not looked at
+  const bool use_momentum = (float)momentum != 0.0f;
+  Rows rows{&params, &grads};
+  if (use_momentum) rows.push_back(&momenta);
+  const TupleInfo info = CheckTuples(
+      "fused_sgd_step", use_momentum ? "grads and momenta" : "grads", rows,
+      false);
+  if (params.empty()) return;
+  c10::hip::HIPGuard guard(info.device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
+  const float* coef = GradCoefPtr(grad_coef, info.device);
+  Batcher<SgdBatchArgs> batch([&](SgdBatchArgs& args) {
+    HIP_CHECK(FusedSgdLaunch(args, (float)lr, (float)momentum,
+                             (float)weight_decay, (float)dampening, nesterov,
+                             coef, stream));
+  });
+  for (size_t i = 0; i < params.size(); ++i) batch.Add(rows, i);
+  batch.Flush();
+}
+
+void FusedAdamwStep(std::vector<at::Tensor>& params,
+                    std::vector<at::Tensor>& grads,
+                    std::vector<at::Tensor>& exp_avgs,
+                    std::vector<at::Tensor>& exp_avg_sqs, double lr,
+                    double beta1, double beta2, double eps,
+                    double weight_decay, int64_t step, at::Tensor grad_coef) {
+  const Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
+  const TupleInfo info = CheckTuples(
+      "fused_adamw_step", "grads, exp_avgs and exp_avg_sqs", rows, false);
+  if (params.empty()) return;
+  c10::hip::HIPGuard guard(info.device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
+  const float* coef = GradCoefPtr(grad_coef, info.device);
+  Batcher<AdamwBatchArgs> batch([&](AdamwBatchArgs& args) {
+    HIP_CHECK(FusedAdamwLaunch(args, (float)lr, (float)beta1, (float)beta2,
+                               (float)eps, (float)weight_decay, step, coef,
+                               stream));
+  });
+  for (size_t i = 0; i < params.size(); ++i) batch.Add(rows, i);
+  batch.Flush();
+}
+
+at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
+                         std::vector<at::Tensor>& grads,
+                         std::vector<at::Tensor>& exp_avgs,
+                         std::vector<at::Tensor>& exp_avg_sqs, double lr,
+                         double beta1, double beta2, double eps,
+                         double weight_decay, int64_t step,
+                         bool bias_correction, bool adapt,
+                         at::Tensor grad_coef) {
+  const Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
+  const TupleInfo info = CheckTuples(
+      "fused_lamb_step", "grads, exp_avgs and exp_avg_sqs", rows, true);
+  if (step < 1)
+    throw std::runtime_error("horovod_amd: fused_lamb_step: step is 1-based");
+  const int64_t n = (int64_t)params.size();
+  c10::hip::HIPGuard guard(info.device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
+  const float* coef = GradCoefPtr(grad_coef, info.device);
+  auto f32 =
+      at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, info.device);
+  // sized for the whole call; every slot is written by exactly one block
+  // before the trust kernel of its batch reads it
+  at::Tensor partials =
+      at::empty({std::max<int64_t>(2 * info.chunk_blocks, 1)}, f32);
+  // empty tensors take no descriptor: their ratio is the preset 1
+  at::Tensor trust = info.any_empty ? at::ones({n}, f32) : at::empty({n}, f32);
+  const LambScalars s =
+      LambFoldScalars((float)lr, (float)beta1, (float)beta2, (float)eps,
+                      (float)weight_decay, step, bias_correction);
+  unsigned long long base = 0;
+  Batcher<LambBatchArgs> batch([&](LambBatchArgs& args) {
+    args.partial_base = base;
+    HIP_CHECK(LambMomentsLaunch(args, s, coef, partials.data_ptr<float>(),
+                                stream));
+    HIP_CHECK(LambTrustLaunch(args, partials.data_ptr<float>(), adapt,
+                              trust.data_ptr<float>(), stream));
+    HIP_CHECK(LambUpdateLaunch(args, s, trust.data_ptr<float>(), stream));
+    base += args.block_prefix[args.count];
+  });
+  for (int64_t i = 0; i < n; ++i) batch.Add(rows, (size_t)i, (unsigned int)i);
+  batch.Flush();
+  return trust;
+}
+
+}  // namespace gpu
+}  // namespace hvd

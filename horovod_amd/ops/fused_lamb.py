@@ -29,107 +29,42 @@ step(), as in FusedAdamW: one native norm pass over all groups, the
 coefficient applied by the step kernel as it reads the gradient.  p.grad is
 left unscaled; the pre-clip norm is kept in `last_grad_norm`.
 """
-import warnings
-
 import torch
 
 from horovod_amd import _core
-from horovod_amd.ops import clip as _clip
+from horovod_amd.ops._fused_base import FusedMomentOptimizer
 
 
-class FusedLAMB(torch.optim.Optimizer):
+class FusedLAMB(FusedMomentOptimizer):
+    _GROUP_DEFAULTS = dict(FusedMomentOptimizer._GROUP_DEFAULTS,
+                           bias_correction=True, always_adapt=False)
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.01, bias_correction=True, always_adapt=False,
                  max_grad_norm=None):
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"invalid betas: {betas}")
-        _clip.check_max_grad_norm(max_grad_norm)
-        # in defaults, hence in every param group: hvd.DistributedOptimizer
-        # rebuilds the optimizer from param_groups alone
-        defaults = dict(lr=lr, betas=betas, eps=eps,
-                        weight_decay=weight_decay,
-                        bias_correction=bias_correction,
-                        always_adapt=always_adapt,
-                        max_grad_norm=max_grad_norm)
-        super().__init__(params, defaults)
-        for group in self.param_groups:   # values given per param group
-            _clip.check_max_grad_norm(group["max_grad_norm"])
-        self.last_grad_norm = None
+        super().__init__(params, dict(
+            lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+            bias_correction=bias_correction, always_adapt=always_adapt,
+            max_grad_norm=max_grad_norm))
 
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        for group in self.param_groups:
-            group.setdefault("bias_correction", True)
-            group.setdefault("always_adapt", False)
-            group.setdefault("max_grad_norm", None)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        clip = None
-        max_grad_norm = _clip.group_max_grad_norm(self.param_groups)
-        if max_grad_norm is not None:
-            clip = _clip.GradClip(
-                [p.grad for group in self.param_groups
-                 for p in group["params"] if p.grad is not None],
-                max_grad_norm)
-            self.last_grad_norm = clip.total_norm
-        for group in self.param_groups:
-            # bucket by bias-correction step: the fused launch applies ONE
-            # step factor, and params restored mid-run can disagree
-            by_step = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state.setdefault(p, {})
-                if "step" not in st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
-                st["step"] += 1
-                if not p.is_cuda or p.dtype != torch.float32 or \
-                        p.grad.is_sparse:
-                    if not getattr(self, "_warned_eager_fallback", False):
-                        self._warned_eager_fallback = True
-                        warnings.warn(
-                            "FusedLAMB: parameter is not CUDA fp32; using "
-                            "the eager (unfused) update for such parameters")
-                    self._eager_update(p, group, st, clip)
-                    continue
-                # torch.optim.AdamW state dicts carry the step as a tensor
-                b = by_step.setdefault(int(st["step"]), ([], [], [], []))
-                b[0].append(p)
-                b[1].append(p.grad)
-                b[2].append(st["exp_avg"])
-                b[3].append(st["exp_avg_sq"])
-            b1, b2 = group["betas"]
-            adapt = group["weight_decay"] != 0 or group["always_adapt"]
-            for step_t, (params, grads, avgs, sqs) in by_step.items():
-                _core.fused_lamb_step(params, grads, avgs, sqs,
-                                      group["lr"], b1, b2, group["eps"],
-                                      group["weight_decay"], step_t,
-                                      group["bias_correction"], adapt,
-                                      clip.kernel_coef(params[0].device)
-                                      if clip else None)
-        return loss
-
-    def _eager_update(self, p, group, st, clip=None):
+    def _fused_update(self, params, group, coef):
         b1, b2 = group["betas"]
-        g = p.grad
-        if g.is_sparse:
-            g = g.to_dense()
-        if clip is not None:
-            g = clip.scaled(g)
-        m, v = st["exp_avg"], st["exp_avg_sq"]
+        adapt = group["weight_decay"] != 0 or group["always_adapt"]
+        for step, ps, grads, avgs, sqs in self._by_step(params):
+            _core.fused_lamb_step(ps, grads, avgs, sqs, group["lr"], b1, b2,
+                                  group["eps"], group["weight_decay"], step,
+                                  group["bias_correction"], adapt, coef)
+
+    def _eager_update(self, p, group, clip):
+        b1, b2 = group["betas"]
+        g = self._eager_grad(p, clip)
+        step, m, v = self._moments(p)
         m.mul_(b1).add_(g, alpha=1 - b1)
         v.mul_(b2).addcmul_(g, g, value=1 - b2)
         bc1 = bc2 = 1.0
         if group["bias_correction"]:
-            bc1 = 1 - b1 ** int(st["step"])
-            bc2 = 1 - b2 ** int(st["step"])
+            bc1 = 1 - b1 ** step
+            bc2 = 1 - b2 ** step
         # 16-bit parameters: u and the two norms in fp32
         acc = p.dtype if p.dtype in (torch.float32, torch.float64) \
             else torch.float32

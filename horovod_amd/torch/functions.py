@@ -103,7 +103,8 @@ def broadcast_optimizer_state(optimizer, root_rank, model=None,
         for group in optimizer.param_groups:
             for p in group["params"]:
                 if p.requires_grad:
-                    p.grad = p.data.new_zeros(p.size())
+                    # in p's layout, as autograd lays gradients out
+                    p.grad = torch.zeros_like(p.data)
                     if (isinstance(optimizer, torch.optim.SparseAdam)
                             or id(p) in sparse_ids):
                         p.grad = p.grad.to_sparse()

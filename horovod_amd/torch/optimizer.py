@@ -130,7 +130,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         name = self._parameter_names.get(p)
         if p.grad is None:
             # fixed-size zero gradient so the collective still matches peers
-            p.grad = p.data.new_zeros(p.shape)
+            p.grad = torch.zeros_like(p.data)
         if p.grad.is_sparse:
             if self.sparse_as_dense:
                 p.grad = p.grad.to_dense()

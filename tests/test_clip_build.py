@@ -1,6 +1,8 @@
 """Global-norm clipping in FusedSGD / FusedAdamW: the native surface exists
 after build() and the option works on CPU parameters through the torch-op
 path (no GPU needed)."""
+import copy
+
 import pytest
 import torch
 
@@ -63,6 +65,65 @@ def test_fused_sgd_clip_matches_torch_cpu():
     with pytest.warns(UserWarning, match="eager"):
         _run(FusedSGD(ps_f, max_grad_norm=1.0, **kw), ps_f,
              torch.optim.SGD(ps_r, **kw), ps_r, rtol=1e-5, atol=1e-6)
+
+
+def test_fused_adamw_continues_torch_adamw_state_dict_cpu():
+    """torch.optim.AdamW keeps `step` as a tensor; FusedAdamW loads that
+    state dict and follows torch from there."""
+    from horovod_amd.ops import FusedAdamW
+    ps_f, ps_r = _params(5)
+    kw = dict(lr=1e-2, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.05)
+    ref = torch.optim.AdamW(ps_r, **kw)
+    for step in range(2):
+        for q, g in zip(ps_r, _grads(step)):
+            q.grad = g.clone()
+        ref.step()
+    assert torch.is_tensor(ref.state[ps_r[0]]["step"])
+    for p, q in zip(ps_f, ps_r):
+        p.data.copy_(q.data)
+    opt = FusedAdamW(ps_f, **kw)
+    # a copy, as if saved and loaded: load_state_dict keeps the step tensor
+    # it is given, and ref goes on counting in its own
+    opt.load_state_dict(copy.deepcopy(ref.state_dict()))
+    assert torch.is_tensor(opt.state[ps_f[0]]["step"])
+    with pytest.warns(UserWarning, match="eager"):
+        for step in range(2, 5):
+            for p, q, g in zip(ps_f, ps_r, _grads(step)):
+                p.grad = g.clone()
+                q.grad = g.clone()
+            opt.step()
+            ref.step()
+            for i, (p, q) in enumerate(zip(ps_f, ps_r)):
+                assert int(opt.state[p]["step"]) == step + 1
+                assert torch.allclose(p, q, rtol=1e-5, atol=1e-6), \
+                    (step, i, (p - q).abs().max().item())
+
+
+@pytest.mark.parametrize("kw", [dict(lr=0.1),
+                                dict(lr=0.1, momentum=0.9, weight_decay=0.01),
+                                dict(lr=0.1, momentum=0.9, nesterov=True)],
+                         ids=["plain", "momentum_wd", "nesterov"])
+def test_fused_sgd_sparse_gradient_matches_torch_on_dense(kw):
+    """A sparse gradient takes the eager update on its densified value."""
+    from horovod_amd.ops import FusedSGD
+    g = torch.Generator().manual_seed(3)
+    p = torch.randn(50, 8, generator=g).requires_grad_(True)
+    q = p.detach().clone().requires_grad_(True)
+    opt, ref = FusedSGD([p], **kw), torch.optim.SGD([q], **kw)
+    with pytest.warns(UserWarning, match="FusedSGD.*eager"):
+        for step in range(3):
+            rows = torch.randperm(50, generator=g)[:7]
+            values = torch.randn(7, 8, generator=g)
+            sparse = torch.sparse_coo_tensor(rows.unsqueeze(0), values,
+                                             (50, 8))
+            p.grad = sparse
+            q.grad = sparse.to_dense()
+            opt.step()
+            ref.step()
+            assert p.grad.is_sparse, "step() must not replace p.grad"
+            assert torch.allclose(p, q, rtol=1e-5, atol=1e-6), \
+                (step, (p - q).abs().max().item())
+    assert not torch.equal(p.detach(), torch.zeros_like(p))
 
 
 DISTRIBUTED_BODY = """
