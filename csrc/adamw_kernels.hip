@@ -9,6 +9,10 @@
 // inv_bc2_sqrt = 1/sqrt(bc2); the per-element arithmetic is adamw_element
 // in multi_tensor.h (torch AdamW definition, denom = sqrt(v)/sqrt(bc2) +
 // eps).
+//
+// Master weights: the same kernel with a 2-byte gradient and a 2-byte model
+// parameter row (LP, multi_tensor.h); fp32 and master-weight launches both
+// move 28 bytes per element.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -19,19 +23,29 @@ namespace gpu {
 
 namespace {
 
-template <bool HAS_COEF>
+template <typename LP>
+using AdamwArgsOf = typename std::conditional<LowPrec<LP>::kModel,
+                                              AdamwMasterBatchArgs,
+                                              AdamwBatchArgs>::type;
+
+template <typename LP, bool HAS_COEF>
 __global__ __launch_bounds__(256) void fused_adamw_k(
-    AdamwBatchArgs args, int blocks_per, float lr, float beta1, float beta2,
+    AdamwArgsOf<LP> args, int blocks_per, float lr, float beta1, float beta2,
     float eps, float weight_decay, float step_size, float inv_bc2_sqrt,
     const float* __restrict__ grad_coef) {
+  using G = typename LowPrec<LP>::Grad;
+  constexpr bool MODEL = LowPrec<LP>::kModel;
+  constexpr int W = LowPrec<LP>::kVec;
   int t = blockIdx.x / blocks_per;
   if (t >= args.count) return;
   // one uniform load; the gradient tensors are never written
   const float coef = HAS_COEF ? *grad_coef : 1.0f;
   float* __restrict__ p = (float*)args.ptr[kRowParam][t];
-  const float* __restrict__ g = (const float*)args.ptr[kRowGrad][t];
+  const G* __restrict__ g = (const G*)args.ptr[kRowGrad][t];
   float* __restrict__ m = (float*)args.ptr[kRowExpAvg][t];
   float* __restrict__ v = (float*)args.ptr[kRowExpAvgSq][t];
+  G* __restrict__ q = nullptr;  // stays null without a model row
+  if constexpr (MODEL) q = (G*)args.ptr[kRowModel][t];
   const long long n = (long long)args.numel[t];
   const long long tid =
       (long long)(blockIdx.x % blocks_per) * blockDim.x + threadIdx.x;
@@ -39,28 +53,53 @@ __global__ __launch_bounds__(256) void fused_adamw_k(
   const float decay = 1.0f - lr * weight_decay;
 
   long long done = 0;
-  if (aligned16(p, g, m, v)) {
-    const long long nvec = n / 4;
-    done = nvec * 4;
+  if (aligned16(p, g, m, v, q)) {
+    const long long nvec = n / W;
+    done = nvec * W;
     for (long long i = tid; i < nvec; i += nthreads) {
-      float4 pv = ((float4*)p)[i];
-      float4 gv = ((const float4*)g)[i];
-      float4 mv = ((float4*)m)[i];
-      float4 vv = ((float4*)v)[i];
+      float pv[W], gv[W], mv[W], vv[W];
+      load_f32_vec(p, i, pv);
+      load_grad_vec(g, i, gv);
+      load_f32_vec(m, i, mv);
+      load_f32_vec(v, i, vv);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        adamw_element<HAS_COEF>((&pv.x)[k], (&gv.x)[k], (&mv.x)[k],
-                                (&vv.x)[k], coef, beta1, beta2, eps, decay,
-                                step_size, inv_bc2_sqrt);
-      ((float4*)p)[i] = pv;
-      ((float4*)m)[i] = mv;
-      ((float4*)v)[i] = vv;
+      for (int k = 0; k < W; ++k)
+        adamw_element<HAS_COEF>(pv[k], gv[k], mv[k], vv[k], coef, beta1, beta2,
+                                eps, decay, step_size, inv_bc2_sqrt);
+      store_f32_vec(p, i, pv);
+      store_f32_vec(m, i, mv);
+      store_f32_vec(v, i, vv);
+      if constexpr (MODEL) store_lp_vec(q, i, pv);
     }
   }
   for (long long i = done + tid; i < n; i += nthreads) {
-    adamw_element<HAS_COEF>(p[i], g[i], m[i], v[i], coef, beta1, beta2, eps,
+    float pe = p[i], me = m[i], ve = v[i];
+    adamw_element<HAS_COEF>(pe, (float)g[i], me, ve, coef, beta1, beta2, eps,
                             decay, step_size, inv_bc2_sqrt);
+    p[i] = pe;
+    m[i] = me;
+    v[i] = ve;
+    if constexpr (MODEL) q[i] = round_lp<G>(pe);
   }
+}
+
+template <typename LP>
+hipError_t launch_adamw(const AdamwArgsOf<LP>& args, float lr, float beta1,
+                        float beta2, float eps, float weight_decay,
+                        long long step, const float* grad_coef,
+                        hipStream_t stream) {
+  if (args.count == 0) return hipSuccess;
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2 = 1.0f - powf(beta2, (float)step);
+  const float step_size = lr / bc1;
+  const float inv_bc2_sqrt = 1.0f / sqrtf(bc2);
+  const int bpc = kBlocksPerTensor;
+  dim3 grid(args.count * bpc), block(256);
+  auto kernel = grad_coef ? fused_adamw_k<LP, true> : fused_adamw_k<LP, false>;
+  kernel<<<grid, block, 0, stream>>>(args, bpc, lr, beta1, beta2, eps,
+                                     weight_decay, step_size, inv_bc2_sqrt,
+                                     grad_coef);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -69,18 +108,26 @@ hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             float beta2, float eps, float weight_decay,
                             long long step, const float* grad_coef,
                             hipStream_t stream) {
-  if (args.count == 0) return hipSuccess;
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2 = 1.0f - powf(beta2, (float)step);
-  const float step_size = lr / bc1;
-  const float inv_bc2_sqrt = 1.0f / sqrtf(bc2);
-  const int bpc = kBlocksPerTensor;
-  dim3 grid(args.count * bpc), block(256);
-  auto kernel = grad_coef ? fused_adamw_k<true> : fused_adamw_k<false>;
-  kernel<<<grid, block, 0, stream>>>(args, bpc, lr, beta1, beta2, eps,
-                                     weight_decay, step_size, inv_bc2_sqrt,
-                                     grad_coef);
-  return hipGetLastError();
+  return launch_adamw<void>(args, lr, beta1, beta2, eps, weight_decay, step,
+                            grad_coef, stream);
+}
+
+hipError_t FusedAdamwMasterLaunch(const AdamwMasterBatchArgs& args, int dt,
+                                  float lr, float beta1, float beta2,
+                                  float eps, float weight_decay,
+                                  long long step, const float* grad_coef,
+                                  hipStream_t stream) {
+  switch (dt) {
+    case DT_F16:
+      return launch_adamw<__half>(args, lr, beta1, beta2, eps, weight_decay,
+                                  step, grad_coef, stream);
+    case DT_BF16:
+      return launch_adamw<__hip_bfloat16>(args, lr, beta1, beta2, eps,
+                                          weight_decay, step, grad_coef,
+                                          stream);
+    default:
+      return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace gpu

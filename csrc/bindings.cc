@@ -147,56 +147,68 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   auto opt_tensor = [](const py::object& o) {
     return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
   };
+  // model_params: None, or the fp16/bf16 model parameters of a master-weight
+  // step (params are then their fp32 masters)
+  using OptTensors = std::optional<std::vector<at::Tensor>>;
+  auto opt_list = [](const OptTensors& o) { return o ? &*o : nullptr; };
   m.def("fused_sgd_step",
-        [opt_tensor](std::vector<at::Tensor> params,
+        [opt_tensor, opt_list](std::vector<at::Tensor> params,
                      std::vector<at::Tensor> grads,
                      std::vector<at::Tensor> momenta, double lr,
                      double momentum, double weight_decay, double dampening,
-                     bool nesterov, py::object grad_coef) {
+                     bool nesterov, py::object grad_coef,
+                     OptTensors model_params) {
           hvd::gpu::FusedSgdStep(params, grads, momenta, lr, momentum,
                                  weight_decay, dampening, nesterov,
-                                 opt_tensor(grad_coef));
+                                 opt_tensor(grad_coef),
+                                 opt_list(model_params));
         },
         py::arg("params"), py::arg("grads"), py::arg("momenta"),
         py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
         py::arg("dampening"), py::arg("nesterov"),
-        py::arg("grad_coef") = py::none());
+        py::arg("grad_coef") = py::none(),
+        py::arg("model_params") = py::none());
 
   m.def("fused_adamw_step",
-        [opt_tensor](std::vector<at::Tensor> params,
+        [opt_tensor, opt_list](std::vector<at::Tensor> params,
                      std::vector<at::Tensor> grads,
                      std::vector<at::Tensor> exp_avgs,
                      std::vector<at::Tensor> exp_avg_sqs, double lr,
                      double beta1, double beta2, double eps,
                      double weight_decay, int64_t step,
-                     py::object grad_coef) {
+                     py::object grad_coef, OptTensors model_params) {
           hvd::gpu::FusedAdamwStep(params, grads, exp_avgs, exp_avg_sqs, lr,
                                    beta1, beta2, eps, weight_decay, step,
-                                   opt_tensor(grad_coef));
+                                   opt_tensor(grad_coef),
+                                   opt_list(model_params));
         },
         py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
         py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
-        py::arg("step"), py::arg("grad_coef") = py::none());
+        py::arg("step"), py::arg("grad_coef") = py::none(),
+        py::arg("model_params") = py::none());
 
   m.def("fused_lamb_step",
-        [opt_tensor](std::vector<at::Tensor> params,
+        [opt_tensor, opt_list](std::vector<at::Tensor> params,
                      std::vector<at::Tensor> grads,
                      std::vector<at::Tensor> exp_avgs,
                      std::vector<at::Tensor> exp_avg_sqs, double lr,
                      double beta1, double beta2, double eps,
                      double weight_decay, int64_t step, bool bias_correction,
-                     bool adapt, py::object grad_coef) {
+                     bool adapt, py::object grad_coef,
+                     OptTensors model_params) {
           return hvd::gpu::FusedLambStep(params, grads, exp_avgs, exp_avg_sqs,
                                          lr, beta1, beta2, eps, weight_decay,
                                          step, bias_correction, adapt,
-                                         opt_tensor(grad_coef));
+                                         opt_tensor(grad_coef),
+                                         opt_list(model_params));
         },
         py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
         py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("step"), py::arg("bias_correction"), py::arg("adapt"),
-        py::arg("grad_coef") = py::none());
+        py::arg("grad_coef") = py::none(),
+        py::arg("model_params") = py::none());
 
   m.def("fused_bn_relu_forward",
         [](at::Tensor x, py::object residual, at::Tensor gamma, at::Tensor beta,

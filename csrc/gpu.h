@@ -106,11 +106,19 @@ void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef);
 // `momenta` is read only when momentum != 0).  grad_coef: undefined, or a
 // 1-element fp32 device tensor the kernel multiplies every gradient element
 // by as it reads it (the gradients are not written).
+//
+// model_params (all three steps): null, or the fp16/bf16 model parameters of
+// a master-weight step.  `params` are then their fp32 masters, the moments
+// stay fp32, grads[i] has the dtype of model_params[i] (fp16 and bf16 may mix
+// within a call; each takes launches of its own), every tuple has one size,
+// device and layout, and the kernels write the updated master, rounded to
+// nearest-even, into the model parameter.
 void FusedSgdStep(std::vector<at::Tensor>& params,
                   std::vector<at::Tensor>& grads,
                   std::vector<at::Tensor>& momenta, double lr, double momentum,
                   double weight_decay, double dampening, bool nesterov,
-                  at::Tensor grad_coef = at::Tensor());
+                  at::Tensor grad_coef = at::Tensor(),
+                  const std::vector<at::Tensor>* model_params = nullptr);
 
 // Fused AdamW step (decoupled weight decay, torch.optim.AdamW math);
 // step is the 1-based step count for bias correction.  grad_coef as in
@@ -121,7 +129,8 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
                     std::vector<at::Tensor>& exp_avg_sqs, double lr,
                     double beta1, double beta2, double eps,
                     double weight_decay, int64_t step,
-                    at::Tensor grad_coef = at::Tensor());
+                    at::Tensor grad_coef = at::Tensor(),
+                    const std::vector<at::Tensor>* model_params = nullptr);
 
 // Fused LAMB step (lamb_kernels.hip): AdamW's moments, then per tensor
 // p -= lr * trust * u with u = mhat / (sqrt(vhat) + eps) + weight_decay * p
@@ -138,7 +147,8 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                          double beta1, double beta2, double eps,
                          double weight_decay, int64_t step,
                          bool bias_correction, bool adapt,
-                         at::Tensor grad_coef = at::Tensor());
+                         at::Tensor grad_coef = at::Tensor(),
+                         const std::vector<at::Tensor>* model_params = nullptr);
 
 }  // namespace gpu
 }  // namespace hvd

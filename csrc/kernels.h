@@ -131,6 +131,9 @@ enum MultiTensorRow {
   kRowMomentum = 2,  // SGD; null when momentum == 0
   kRowExpAvg = 2,    // AdamW, LAMB
   kRowExpAvgSq = 3,
+  // master-weight kernels: the fp16/bf16 model parameter, written only
+  kRowSgdModel = 3,
+  kRowModel = 4,  // AdamW, LAMB
 };
 
 using ClipBatchArgs = MultiTensorArgs<1, true>;
@@ -141,6 +144,18 @@ static_assert(sizeof(ClipBatchArgs) == 984 && sizeof(SgdBatchArgs) == 1544 &&
                   sizeof(AdamwBatchArgs) == 1928 && sizeof(LambBatchArgs) == 2328,
               "kernarg bytes of the four structs these replaced");
 
+// Master-weight launches (fp32 master in kRowParam, 2-byte gradient, 2-byte
+// model parameter in one more row): by value like the above, so they too must
+// stay well under the 4 KB kernarg limit.
+using SgdMasterBatchArgs = MultiTensorArgs<4, false>;
+using AdamwMasterBatchArgs = MultiTensorArgs<5, false>;
+using LambMasterBatchArgs = MultiTensorArgs<5, true, true>;
+static_assert(sizeof(SgdMasterBatchArgs) == 1928 &&
+                  sizeof(AdamwMasterBatchArgs) == 2312 &&
+                  sizeof(LambMasterBatchArgs) == 2712,
+              "kernarg bytes: one 384-byte pointer row more than the fp32 "
+              "structs, under 4 KB");
+
 // ---- Fused SGD (sgd_kernels.hip) ------------------------------------------
 // grad_coef: null, or a device fp32 scalar every gradient element is
 // multiplied by (the global-norm clip coefficient) before weight decay and
@@ -148,6 +163,14 @@ static_assert(sizeof(ClipBatchArgs) == 984 && sizeof(SgdBatchArgs) == 1544 &&
 hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
                           float weight_decay, float dampening, bool nesterov,
                           const float* grad_coef, hipStream_t stream);
+// Master weights: the same kernel instantiated for dt in {DT_F16, DT_BF16}.
+// kRowParam holds the fp32 master, kRowGrad a gradient of type dt (widened
+// exactly as it is read), kRowSgdModel the model parameter of type dt, which
+// receives the updated master rounded to nearest-even.  One dt per launch.
+hipError_t FusedSgdMasterLaunch(const SgdMasterBatchArgs& args, int dt,
+                                float lr, float momentum, float weight_decay,
+                                float dampening, bool nesterov,
+                                const float* grad_coef, hipStream_t stream);
 
 // ---- Fused AdamW (adamw_kernels.hip) --------------------------------------
 // step is 1-based (bias correction uses beta^step).  grad_coef as in
@@ -156,6 +179,12 @@ hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             float beta2, float eps, float weight_decay,
                             long long step, const float* grad_coef,
                             hipStream_t stream);
+// Master weights, as FusedSgdMasterLaunch; the model parameter is kRowModel.
+hipError_t FusedAdamwMasterLaunch(const AdamwMasterBatchArgs& args, int dt,
+                                  float lr, float beta1, float beta2,
+                                  float eps, float weight_decay,
+                                  long long step, const float* grad_coef,
+                                  hipStream_t stream);
 
 // ---- Global-norm gradient clipping (clip_kernels.hip) ----------------------
 // Chunked.  One row; tensors are dense, of one dtype per launch (dt in
@@ -178,7 +207,8 @@ hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
                             const float* coef, hipStream_t stream);
 
 // ---- Fused LAMB (lamb_kernels.hip) -----------------------------------------
-// Chunked.  Three launches per batch, all fp32:
+// Chunked.  Three launches per batch, all fp32 (but see the master-weight
+// launches below):
 //   1. moments + norms: m, v updated in place, u = mhat / (sqrt(vhat) + eps)
 //      + weight_decay * p formed in registers; block b writes sum(p^2) and
 //      sum(u^2) of its chunk to partials[2 * (partial_base + b) + {0, 1}]
@@ -206,6 +236,20 @@ hipError_t LambTrustLaunch(const LambBatchArgs& args, const float* partials,
                            bool adapt, float* trust, hipStream_t stream);
 hipError_t LambUpdateLaunch(const LambBatchArgs& args, const LambScalars& s,
                             const float* trust, hipStream_t stream);
+// Master weights (dt in {DT_F16, DT_BF16}, one per launch): pass 1 reads the
+// fp32 master and a gradient of type dt, so norms and trust ratios are the
+// master's; pass 3 writes the master and, rounded to nearest-even, the model
+// parameter of type dt in kRowModel.
+hipError_t LambMomentsMasterLaunch(const LambMasterBatchArgs& args, int dt,
+                                   const LambScalars& s,
+                                   const float* grad_coef, float* partials,
+                                   hipStream_t stream);
+hipError_t LambTrustLaunch(const LambMasterBatchArgs& args,
+                           const float* partials, bool adapt, float* trust,
+                           hipStream_t stream);
+hipError_t LambUpdateMasterLaunch(const LambMasterBatchArgs& args, int dt,
+                                  const LambScalars& s, const float* trust,
+                                  hipStream_t stream);
 
 // ---- Fused BatchNorm(+Add)+ReLU (bn_kernels.hip) --------------------------
 // NHWC dense activations [total=N*H*W rows, C channels], C % 8 == 0,

@@ -20,6 +20,11 @@
 //
 // Bias correction is folded on the host into inv_bc1 and inv_bc2_sqrt, so
 // the per-element body is one sqrtf, one divide and FMAs.
+//
+// Master weights (LP, multi_tensor.h): p is the fp32 master, 1. reads a
+// 2-byte gradient, norms and trust ratios are the master's, and 3. also
+// writes the rounded master into the 2-byte model parameter.  The bytes
+// moved stay 40 per element (22 + 18 instead of 24 + 16).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,47 +39,53 @@ namespace {
 
 constexpr int kTrustThreads = 256;
 
-template <bool HAS_COEF>
+template <typename LP>
+using LambArgsOf = typename std::conditional<LowPrec<LP>::kModel,
+                                             LambMasterBatchArgs,
+                                             LambBatchArgs>::type;
+
+// LP: void, or the 2-byte type of the gradient and the model parameter
+// (master weights, multi_tensor.h); p is then the fp32 master.
+template <typename LP, bool HAS_COEF>
 __global__ __launch_bounds__(kChunkThreads) void lamb_moments_k(
-    LambBatchArgs args, LambScalars s, const float* __restrict__ grad_coef,
+    LambArgsOf<LP> args, LambScalars s, const float* __restrict__ grad_coef,
     float* __restrict__ partials) {
+  using G = typename LowPrec<LP>::Grad;
+  constexpr int W = LowPrec<LP>::kVec;
   const ChunkRef c = find_chunk(args);
   // one uniform load; the gradient tensors are never written
   const float coef = HAS_COEF ? *grad_coef : 1.0f;
   const float* __restrict__ p = (const float*)args.ptr[kRowParam][c.tensor];
-  const float* __restrict__ g = (const float*)args.ptr[kRowGrad][c.tensor];
+  const G* __restrict__ g = (const G*)args.ptr[kRowGrad][c.tensor];
   float* __restrict__ m = (float*)args.ptr[kRowExpAvg][c.tensor];
   float* __restrict__ v = (float*)args.ptr[kRowExpAvgSq][c.tensor];
 
-  // independent accumulators, one per lane of the 16-byte vector
+  // independent accumulators, one per lane of a 16-byte fp32 vector
   float pp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float uu[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   long long done = c.begin;
   // chunk starts are multiples of kChunkElems elements, so the chunk is
   // 16-byte aligned exactly when the tensor is
   if (aligned16(p, g, m, v)) {
-    const long long nvec = (c.end - c.begin) / 4;
-    const float4* __restrict__ p4 = (const float4*)(p + c.begin);
-    const float4* __restrict__ g4 = (const float4*)(g + c.begin);
-    float4* __restrict__ m4 = (float4*)(m + c.begin);
-    float4* __restrict__ v4 = (float4*)(v + c.begin);
-    done = c.begin + nvec * 4;
+    const long long nvec = (c.end - c.begin) / W;
+    done = c.begin + nvec * W;
     for (long long i = threadIdx.x; i < nvec; i += kChunkThreads) {
-      const float4 pv = p4[i];
-      const float4 gv = g4[i];
-      float4 mv = m4[i];
-      float4 vv = v4[i];
+      float pv[W], gv[W], mv[W], vv[W];
+      load_f32_vec(p + c.begin, i, pv);
+      load_grad_vec(g + c.begin, i, gv);
+      load_f32_vec(m + c.begin, i, mv);
+      load_f32_vec(v + c.begin, i, vv);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        lamb_moments_element<HAS_COEF>((&pv.x)[k], (&gv.x)[k], (&mv.x)[k],
-                                       (&vv.x)[k], coef, s, pp[k], uu[k]);
-      m4[i] = mv;
-      v4[i] = vv;
+      for (int k = 0; k < W; ++k)
+        lamb_moments_element<HAS_COEF>(pv[k], gv[k], mv[k], vv[k], coef, s,
+                                       pp[k & 3], uu[k & 3]);
+      store_f32_vec(m + c.begin, i, mv);
+      store_f32_vec(v + c.begin, i, vv);
     }
   }
   for (long long i = done + threadIdx.x; i < c.end; i += kChunkThreads) {
-    lamb_moments_element<HAS_COEF>(p[i], g[i], m[i], v[i], coef, s, pp[0],
-                                   uu[0]);
+    lamb_moments_element<HAS_COEF>(p[i], (float)g[i], m[i], v[i], coef, s,
+                                   pp[0], uu[0]);
   }
   const float pp_total = block_sum((pp[0] + pp[1]) + (pp[2] + pp[3]));
   // block_sum's LDS is shared by both calls: thread 0 must be done reading
@@ -89,9 +100,10 @@ __global__ __launch_bounds__(kChunkThreads) void lamb_moments_k(
 
 // Block t handles tensor t of the batch: thread i sums the slot pairs i,
 // i + 256, ... of the tensor in fp64 (a 31 M-element embedding has ~3800),
-// then a fixed LDS tree.
+// then a fixed LDS tree.  Args: LambBatchArgs or LambMasterBatchArgs.
+template <typename Args>
 __global__ __launch_bounds__(kTrustThreads) void lamb_trust_k(
-    LambBatchArgs args, const float* __restrict__ partials, bool adapt,
+    Args args, const float* __restrict__ partials, bool adapt,
     float* __restrict__ trust) {
   __shared__ double part_p[kTrustThreads];
   __shared__ double part_u[kTrustThreads];
@@ -124,36 +136,73 @@ __global__ __launch_bounds__(kTrustThreads) void lamb_trust_k(
   }
 }
 
+// With LP the updated master also goes to the model parameter, rounded.
+template <typename LP>
 __global__ __launch_bounds__(kChunkThreads) void lamb_update_k(
-    LambBatchArgs args, LambScalars s, const float* __restrict__ trust) {
+    LambArgsOf<LP> args, LambScalars s, const float* __restrict__ trust) {
+  using Q = typename LowPrec<LP>::Grad;
+  constexpr bool MODEL = LowPrec<LP>::kModel;
+  constexpr int W = LowPrec<LP>::kVec;
   const ChunkRef c = find_chunk(args);
   const float step = s.lr * trust[args.out_index[c.tensor]];
   float* __restrict__ p = (float*)args.ptr[kRowParam][c.tensor];
   const float* __restrict__ m = (const float*)args.ptr[kRowExpAvg][c.tensor];
   const float* __restrict__ v = (const float*)args.ptr[kRowExpAvgSq][c.tensor];
+  Q* __restrict__ q = nullptr;  // stays null without a model row
+  if constexpr (MODEL) q = (Q*)args.ptr[kRowModel][c.tensor];
 
   long long done = c.begin;
-  if (aligned16(p, m, v)) {
-    const long long nvec = (c.end - c.begin) / 4;
-    float4* __restrict__ p4 = (float4*)(p + c.begin);
-    const float4* __restrict__ m4 = (const float4*)(m + c.begin);
-    const float4* __restrict__ v4 = (const float4*)(v + c.begin);
-    done = c.begin + nvec * 4;
+  if (aligned16(p, m, v, q)) {
+    const long long nvec = (c.end - c.begin) / W;
+    done = c.begin + nvec * W;
     for (long long i = threadIdx.x; i < nvec; i += kChunkThreads) {
-      float4 pv = p4[i];
-      const float4 mv = m4[i];
-      const float4 vv = v4[i];
+      float pv[W], mv[W], vv[W];
+      load_f32_vec(p + c.begin, i, pv);
+      load_f32_vec(m + c.begin, i, mv);
+      load_f32_vec(v + c.begin, i, vv);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        lamb_update_element((&pv.x)[k], (&mv.x)[k], (&vv.x)[k], step, s);
-      p4[i] = pv;
+      for (int k = 0; k < W; ++k)
+        lamb_update_element(pv[k], mv[k], vv[k], step, s);
+      store_f32_vec(p + c.begin, i, pv);
+      if constexpr (MODEL) store_lp_vec(q + c.begin, i, pv);
     }
   }
   for (long long i = done + threadIdx.x; i < c.end; i += kChunkThreads) {
     float pe = p[i];
     lamb_update_element(pe, m[i], v[i], step, s);
     p[i] = pe;
+    if constexpr (MODEL) q[i] = round_lp<Q>(pe);
   }
+}
+
+template <typename LP>
+hipError_t launch_moments(const LambArgsOf<LP>& args, const LambScalars& s,
+                          const float* grad_coef, float* partials,
+                          hipStream_t stream) {
+  if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
+  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
+  auto kernel =
+      grad_coef ? lamb_moments_k<LP, true> : lamb_moments_k<LP, false>;
+  kernel<<<grid, block, 0, stream>>>(args, s, grad_coef, partials);
+  return hipGetLastError();
+}
+
+template <typename Args>
+hipError_t launch_trust(const Args& args, const float* partials, bool adapt,
+                        float* trust, hipStream_t stream) {
+  if (args.count == 0) return hipSuccess;
+  lamb_trust_k<Args><<<dim3(args.count), dim3(kTrustThreads), 0, stream>>>(
+      args, partials, adapt, trust);
+  return hipGetLastError();
+}
+
+template <typename LP>
+hipError_t launch_update(const LambArgsOf<LP>& args, const LambScalars& s,
+                         const float* trust, hipStream_t stream) {
+  if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
+  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
+  lamb_update_k<LP><<<grid, block, 0, stream>>>(args, s, trust);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -181,27 +230,51 @@ LambScalars LambFoldScalars(float lr, float beta1, float beta2, float eps,
 hipError_t LambMomentsLaunch(const LambBatchArgs& args, const LambScalars& s,
                              const float* grad_coef, float* partials,
                              hipStream_t stream) {
-  if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
-  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
-  auto kernel = grad_coef ? lamb_moments_k<true> : lamb_moments_k<false>;
-  kernel<<<grid, block, 0, stream>>>(args, s, grad_coef, partials);
-  return hipGetLastError();
+  return launch_moments<void>(args, s, grad_coef, partials, stream);
 }
 
 hipError_t LambTrustLaunch(const LambBatchArgs& args, const float* partials,
                            bool adapt, float* trust, hipStream_t stream) {
-  if (args.count == 0) return hipSuccess;
-  lamb_trust_k<<<dim3(args.count), dim3(kTrustThreads), 0, stream>>>(
-      args, partials, adapt, trust);
-  return hipGetLastError();
+  return launch_trust(args, partials, adapt, trust, stream);
 }
 
 hipError_t LambUpdateLaunch(const LambBatchArgs& args, const LambScalars& s,
                             const float* trust, hipStream_t stream) {
-  if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
-  dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
-  lamb_update_k<<<grid, block, 0, stream>>>(args, s, trust);
-  return hipGetLastError();
+  return launch_update<void>(args, s, trust, stream);
+}
+
+hipError_t LambMomentsMasterLaunch(const LambMasterBatchArgs& args, int dt,
+                                   const LambScalars& s,
+                                   const float* grad_coef, float* partials,
+                                   hipStream_t stream) {
+  switch (dt) {
+    case DT_F16:
+      return launch_moments<__half>(args, s, grad_coef, partials, stream);
+    case DT_BF16:
+      return launch_moments<__hip_bfloat16>(args, s, grad_coef, partials,
+                                            stream);
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+hipError_t LambTrustLaunch(const LambMasterBatchArgs& args,
+                           const float* partials, bool adapt, float* trust,
+                           hipStream_t stream) {
+  return launch_trust(args, partials, adapt, trust, stream);
+}
+
+hipError_t LambUpdateMasterLaunch(const LambMasterBatchArgs& args, int dt,
+                                  const LambScalars& s, const float* trust,
+                                  hipStream_t stream) {
+  switch (dt) {
+    case DT_F16:
+      return launch_update<__half>(args, s, trust, stream);
+    case DT_BF16:
+      return launch_update<__hip_bfloat16>(args, s, trust, stream);
+    default:
+      return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace gpu

@@ -43,11 +43,14 @@ struct TupleInfo {
 };
 
 // What the optimizer kernels need of the tuples (rows[0][i], rows[1][i], ...),
-// rows[0] being the parameters and `others` naming the rest: lists of one
-// length, dense fp32 tensors on one GPU, each tuple of one size and layout
-// (the kernels walk memory order), and for `chunked` kernels the size limit.
+// rows[0] being the parameters, rows[1] the gradients and `others` naming the
+// rest: lists of one length, dense fp32 tensors on one GPU, each tuple of one
+// size and layout (the kernels walk memory order), and for `chunked` kernels
+// the size limit.  With `models` (master weights) rows[0] are the fp32
+// masters, and models[i] and its gradient share one 2-byte dtype.
 TupleInfo CheckTuples(const std::string& op, const char* others,
-                      const Rows& rows, bool chunked) {
+                      const Rows& rows, bool chunked,
+                      const TensorList* models = nullptr) {
   auto fail = [&op](const std::string& what) {
     throw std::runtime_error("horovod_amd: " + op + what);
   };
@@ -56,15 +59,29 @@ TupleInfo CheckTuples(const std::string& op, const char* others,
   for (const TensorList* list : rows)
     if (list->size() != n)
       fail(std::string(" needs as many ") + others + " as params");
+  if (models && models->size() != n)
+    fail(" needs as many model_params as params");
+  Rows all = rows;
+  if (models) all.push_back(models);
   TupleInfo info{n == 0 ? (int)c10::hip::current_device() : -1, 0, false};
   for (size_t i = 0; i < n; ++i) {
     const at::Tensor& p = params[i];
-    for (const TensorList* list : rows) {
+    if (models && (*models)[i].scalar_type() != at::kHalf &&
+        (*models)[i].scalar_type() != at::kBFloat16)
+      fail(" needs fp16 or bf16 model_params");
+    for (const TensorList* list : all) {
       const at::Tensor& t = (*list)[i];
       if (info.device < 0 && t.is_cuda()) info.device = (int)t.get_device();
       if (!t.is_cuda() || t.is_sparse() || t.get_device() != info.device)
         fail(" needs dense tensors on one GPU");
-      if (t.scalar_type() != at::kFloat) fail(" supports fp32 tensors only");
+      if (!models) {
+        if (t.scalar_type() != at::kFloat) fail(" supports fp32 tensors only");
+      } else if (list == rows[1]) {
+        if (t.scalar_type() != (*models)[i].scalar_type())
+          fail(" needs a gradient of its model parameter's dtype");
+      } else if (list != models && t.scalar_type() != at::kFloat) {
+        fail(" with model_params needs fp32 masters and moments");
+      }
       const bool same_layout =
           (t.is_contiguous() && p.is_contiguous()) ||
           (t.sizes() == p.sizes() && t.strides() == p.strides());
@@ -91,7 +108,8 @@ class Batcher {
   explicit Batcher(std::function<void(Args&)> launch)
       : launch_(std::move(launch)) {}
 
-  // Tuple i of `rows`; `index`: its slot in an indexed per-tensor output.
+  // Tuple i of `rows` (a null row gives null pointers); `index`: its slot in
+  // an indexed per-tensor output.
   void Add(const Rows& rows, size_t i, unsigned int index = 0) {
     const int64_t numel = (*rows[0])[i].numel();
     if (numel == 0) return;
@@ -103,7 +121,8 @@ class Batcher {
     }
     const int k = args_.count++;
     for (size_t r = 0; r < (size_t)Args::kRows; ++r)
-      args_.ptr[r][k] = r < rows.size() ? (*rows[r])[i].data_ptr() : nullptr;
+      args_.ptr[r][k] =
+          r < rows.size() && rows[r] ? (*rows[r])[i].data_ptr() : nullptr;
     args_.numel[k] = (unsigned long long)numel;
     if constexpr (Args::kChunked)
       args_.block_prefix[k + 1] = args_.block_prefix[k] + (unsigned int)blocks;
@@ -158,6 +177,23 @@ void ForEachClipBatch(const TensorList& tensors, int device,
   for (auto& b : batch) b.Flush();
 }
 
+// Master weights: one launch handles one 2-byte dtype, so the tuples go to a
+// Batcher per dtype.  launch(args, dt) as above; rows.back() are the model
+// parameters.
+template <typename Args>
+void ForEachMasterBatch(const Rows& rows, bool indexed,
+                        const std::function<void(Args&, int)>& launch) {
+  auto of = [&launch](int dt) {
+    return Batcher<Args>([&launch, dt](Args& args) { launch(args, dt); });
+  };
+  Batcher<Args> batch[2] = {of(DT_F16), of(DT_BF16)};
+  const TensorList& models = *rows.back();
+  for (size_t i = 0; i < models.size(); ++i)
+    batch[models[i].scalar_type() == at::kHalf ? 0 : 1].Add(
+        rows, i, indexed ? (unsigned int)i : 0);
+  for (auto& b : batch) b.Flush();
+}
+
 }  // namespace
 
 at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
@@ -200,7 +236,8 @@ void FusedSgdStep(std::vector<at::Tensor>& params,
                   std::vector<at::Tensor>& grads,
                   std::vector<at::Tensor>& momenta, double lr, double momentum,
                   double weight_decay, double dampening, bool nesterov,
-                  at::Tensor grad_coef) {
+                  at::Tensor grad_coef,
+                  const std::vector<at::Tensor>* model_params) {
   // the kernel reads the momentum row exactly when the launcher sees a
   // nonzero fp32 momentum; without it `momenta` is not looked at
   const bool use_momentum = (float)momentum != 0.0f;
@@ -208,11 +245,22 @@ void FusedSgdStep(std::vector<at::Tensor>& params,
   if (use_momentum) rows.push_back(&momenta);
   const TupleInfo info = CheckTuples(
       "fused_sgd_step", use_momentum ? "grads and momenta" : "grads", rows,
-      false);
+      false, model_params);
   if (params.empty()) return;
   c10::hip::HIPGuard guard(info.device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
   const float* coef = GradCoefPtr(grad_coef, info.device);
+  if (model_params) {
+    rows = {&params, &grads, use_momentum ? &momenta : nullptr, model_params};
+    ForEachMasterBatch<SgdMasterBatchArgs>(
+        rows, false, [&](SgdMasterBatchArgs& args, int dt) {
+          HIP_CHECK(FusedSgdMasterLaunch(args, dt, (float)lr, (float)momentum,
+                                         (float)weight_decay,
+                                         (float)dampening, nesterov, coef,
+                                         stream));
+        });
+    return;
+  }
   Batcher<SgdBatchArgs> batch([&](SgdBatchArgs& args) {
     HIP_CHECK(FusedSgdLaunch(args, (float)lr, (float)momentum,
                              (float)weight_decay, (float)dampening, nesterov,
@@ -227,14 +275,27 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
                     std::vector<at::Tensor>& exp_avgs,
                     std::vector<at::Tensor>& exp_avg_sqs, double lr,
                     double beta1, double beta2, double eps,
-                    double weight_decay, int64_t step, at::Tensor grad_coef) {
-  const Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
-  const TupleInfo info = CheckTuples(
-      "fused_adamw_step", "grads, exp_avgs and exp_avg_sqs", rows, false);
+                    double weight_decay, int64_t step, at::Tensor grad_coef,
+                    const std::vector<at::Tensor>* model_params) {
+  Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
+  const TupleInfo info =
+      CheckTuples("fused_adamw_step", "grads, exp_avgs and exp_avg_sqs", rows,
+                  false, model_params);
   if (params.empty()) return;
   c10::hip::HIPGuard guard(info.device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
   const float* coef = GradCoefPtr(grad_coef, info.device);
+  if (model_params) {
+    rows.push_back(model_params);
+    ForEachMasterBatch<AdamwMasterBatchArgs>(
+        rows, false, [&](AdamwMasterBatchArgs& args, int dt) {
+          HIP_CHECK(FusedAdamwMasterLaunch(args, dt, (float)lr, (float)beta1,
+                                           (float)beta2, (float)eps,
+                                           (float)weight_decay, step, coef,
+                                           stream));
+        });
+    return;
+  }
   Batcher<AdamwBatchArgs> batch([&](AdamwBatchArgs& args) {
     HIP_CHECK(FusedAdamwLaunch(args, (float)lr, (float)beta1, (float)beta2,
                                (float)eps, (float)weight_decay, step, coef,
@@ -251,10 +312,12 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                          double beta1, double beta2, double eps,
                          double weight_decay, int64_t step,
                          bool bias_correction, bool adapt,
-                         at::Tensor grad_coef) {
-  const Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
-  const TupleInfo info = CheckTuples(
-      "fused_lamb_step", "grads, exp_avgs and exp_avg_sqs", rows, true);
+                         at::Tensor grad_coef,
+                         const std::vector<at::Tensor>* model_params) {
+  Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
+  const TupleInfo info =
+      CheckTuples("fused_lamb_step", "grads, exp_avgs and exp_avg_sqs", rows,
+                  true, model_params);
   if (step < 1)
     throw std::runtime_error("horovod_amd: fused_lamb_step: step is 1-based");
   const int64_t n = (int64_t)params.size();
@@ -273,6 +336,21 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
       LambFoldScalars((float)lr, (float)beta1, (float)beta2, (float)eps,
                       (float)weight_decay, step, bias_correction);
   unsigned long long base = 0;
+  if (model_params) {
+    rows.push_back(model_params);
+    ForEachMasterBatch<LambMasterBatchArgs>(
+        rows, true, [&](LambMasterBatchArgs& args, int dt) {
+          args.partial_base = base;
+          HIP_CHECK(LambMomentsMasterLaunch(
+              args, dt, s, coef, partials.data_ptr<float>(), stream));
+          HIP_CHECK(LambTrustLaunch(args, partials.data_ptr<float>(), adapt,
+                                    trust.data_ptr<float>(), stream));
+          HIP_CHECK(LambUpdateMasterLaunch(args, dt, s,
+                                           trust.data_ptr<float>(), stream));
+          base += args.block_prefix[args.count];
+        });
+    return trust;
+  }
   Batcher<LambBatchArgs> batch([&](LambBatchArgs& args) {
     args.partial_base = base;
     HIP_CHECK(LambMomentsLaunch(args, s, coef, partials.data_ptr<float>(),

@@ -5,6 +5,10 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -64,16 +68,112 @@ __device__ __forceinline__ bool aligned16(const P*... p) {
   return ((... | (uintptr_t)p) & 15) == 0;
 }
 
+// x as a value of its own: the empty asm keeps the compiler from fusing the
+// operation that made it into a later one.
+__device__ __forceinline__ float pinned(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+// ---- master weights ----------------------------------------------------------
+// The optimizer kernels are templates on LP, the 2-byte type of the model
+// parameter and its gradient (__half or __hip_bfloat16), or void for fp32
+// parameters.  With LP the fp32 rows hold the master and the moments, the
+// gradient is widened exactly as it is read, and the updated master also
+// goes, rounded to nearest-even, to the model-parameter row.  The 16-byte
+// loop then takes 8 elements per lane: one 16-byte access on each 2-byte row,
+// two on each fp32 row.
+template <typename LP>
+struct LowPrec {
+  static constexpr bool kModel = true;
+  static constexpr int kVec = 8;  // elements per lane in the 16-byte loop
+  using Grad = LP;
+};
+template <>
+struct LowPrec<void> {
+  static constexpr bool kModel = false;
+  static constexpr int kVec = 4;
+  using Grad = float;  // also the placeholder type of the absent model row
+};
+
+// x[0..W) = base[i * W ...] as W / 4 16-byte loads, and the matching store.
+template <int W>
+__device__ __forceinline__ void load_f32_vec(const float* base, long long i,
+                                             float (&x)[W]) {
+#pragma unroll
+  for (int q = 0; q < W / 4; ++q) {
+    const float4 v = ((const float4*)base)[i * (W / 4) + q];
+    x[4 * q] = v.x;
+    x[4 * q + 1] = v.y;
+    x[4 * q + 2] = v.z;
+    x[4 * q + 3] = v.w;
+  }
+}
+template <int W>
+__device__ __forceinline__ void store_f32_vec(float* base, long long i,
+                                              const float (&x)[W]) {
+#pragma unroll
+  for (int q = 0; q < W / 4; ++q)
+    ((float4*)base)[i * (W / 4) + q] =
+        float4{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+}
+// The same for 8 values of a 2-byte type in one 16-byte access: widening is
+// exact, the store rounds to nearest-even.  round_lp converts a value that
+// has also been stored as fp32: pinned first, since an fma fused with the
+// conversion would round once, from the exact result, and the model
+// parameter would not be the rounded master.
+template <typename T>
+__device__ __forceinline__ T round_lp(float x) {
+  return (T)pinned(x);
+}
+template <typename T>
+__device__ __forceinline__ void load_lp_vec(const T* base, long long i,
+                                            float (&x)[8]) {
+  static_assert(sizeof(T) == 2, "fp16 or bf16");
+  union {
+    uint4 u;
+    T e[8];
+  } in;
+  in.u = ((const uint4*)base)[i];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x[k] = (float)in.e[k];
+}
+template <typename T>
+__device__ __forceinline__ void store_lp_vec(T* base, long long i,
+                                             const float (&x)[8]) {
+  static_assert(sizeof(T) == 2, "fp16 or bf16");
+  union {
+    uint4 u;
+    T e[8];
+  } out;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out.e[k] = round_lp<T>(x[k]);
+  ((uint4*)base)[i] = out.u;
+}
+// A gradient row: fp32 (W = 4) or 2-byte (W = 8).
+template <typename G, int W>
+__device__ __forceinline__ void load_grad_vec(const G* base, long long i,
+                                              float (&x)[W]) {
+  if constexpr (std::is_same<G, float>::value)
+    load_f32_vec(base, i, x);
+  else
+    load_lp_vec(base, i, x);
+}
+
 // ---- per-element arithmetic -------------------------------------------------
 
-// g * coef as a value of its own: the empty asm keeps the compiler from
-// contracting the product into a later fma (the weight-decay add, the
-// moment updates), so a clip coefficient of exactly 1 reproduces the
-// unclipped update bit for bit.
+// The fused multiply-adds below are written out.  Left to contraction, a sum
+// of two products may have either one fused, and the compiler chooses
+// differently from one loop or instantiation to the next; stated as fmaf the
+// 16-byte loop and the tail loop of every instantiation (fp32, fp16, bf16)
+// compute the same bits, those of the fp32 16-byte loops before there were
+// others.
+
+// g * coef, never contracted into the weight-decay add or the moment
+// updates, so a clip coefficient of exactly 1 reproduces the unclipped
+// update bit for bit.
 __device__ __forceinline__ float scale_grad(float g, float coef) {
-  float r = g * coef;
-  asm("" : "+v"(r));
-  return r;
+  return pinned(g * coef);
 }
 
 // torch.optim.SGD: weight decay into the gradient, momentum buffer, update.
@@ -83,19 +183,19 @@ __device__ __forceinline__ void sgd_element(float& p, float g, float& m,
                                             float momentum, float weight_decay,
                                             float dampening) {
   if (HAS_COEF) g = scale_grad(g, coef);
-  g += weight_decay * p;
+  g = fmaf(weight_decay, p, g);
   if (HAS_MOMENTUM) {
-    m = momentum * m + (1.0f - dampening) * g;
-    g = NESTEROV ? g + momentum * m : m;
+    m = fmaf(momentum, m, (1.0f - dampening) * g);
+    g = NESTEROV ? fmaf(momentum, m, g) : m;
   }
-  p = p - lr * g;
+  p = fmaf(-lr, g, p);
 }
 
 // Adam's two moments (AdamW and LAMB).
 __device__ __forceinline__ void adam_moments(float& m, float& v, float g,
                                              float beta1, float beta2) {
-  m = beta1 * m + (1.0f - beta1) * g;
-  v = beta2 * v + (1.0f - beta2) * g * g;
+  m = fmaf(1.0f - beta1, g, beta1 * m);
+  v = fmaf((1.0f - beta2) * g, g, beta2 * v);
 }
 
 // torch.optim.AdamW with the bias correction folded on the host: decay =
@@ -113,8 +213,8 @@ __device__ __forceinline__ void adamw_element(float& p, float g, float& m,
   adam_moments(me, ve, g, beta1, beta2);
   m = me;
   v = ve;
-  const float denom = sqrtf(ve) * inv_bc2_sqrt + eps;
-  p = p * decay - step_size * me / denom;
+  const float denom = fmaf(sqrtf(ve), inv_bc2_sqrt, eps);
+  p = fmaf(p, decay, -(step_size * me / denom));
 }
 
 // LAMB's u from the already-updated moments.
@@ -145,7 +245,7 @@ __device__ __forceinline__ void lamb_moments_element(float p, float g,
 __device__ __forceinline__ void lamb_update_element(float& p, float m, float v,
                                                     float step,
                                                     const LambScalars& s) {
-  p = p - step * lamb_u(p, m, v, s);
+  p = fmaf(-step, lamb_u(p, m, v, s), p);
 }
 
 }  // namespace gpu

@@ -28,6 +28,11 @@ max_grad_norm=<float> clips by the global L2 norm of all gradients inside
 step(), as in FusedAdamW: one native norm pass over all groups, the
 coefficient applied by the step kernel as it reads the gradient.  p.grad is
 left unscaled; the pre-clip norm is kept in `last_grad_norm`.
+
+master_weights=True keeps an fp32 `master_param` and fp32 moments for every
+fp16/bf16 parameter.  p in the definition above is then the master: norms and
+trust ratios are the master's, and the last launch writes the master and,
+rounded to nearest-even, the parameter (see _fused_base.py).
 """
 import torch
 
@@ -41,23 +46,26 @@ class FusedLAMB(FusedMomentOptimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.01, bias_correction=True, always_adapt=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, master_weights=False):
         super().__init__(params, dict(
             lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
             bias_correction=bias_correction, always_adapt=always_adapt,
-            max_grad_norm=max_grad_norm))
+            max_grad_norm=max_grad_norm, master_weights=master_weights))
 
-    def _fused_update(self, params, group, coef):
+    def _fused_update(self, params, group, coef, master):
         b1, b2 = group["betas"]
         adapt = group["weight_decay"] != 0 or group["always_adapt"]
-        for step, ps, grads, avgs, sqs in self._by_step(params):
-            _core.fused_lamb_step(ps, grads, avgs, sqs, group["lr"], b1, b2,
+        for step, ws, grads, avgs, sqs, models in self._by_step(params,
+                                                                 master):
+            _core.fused_lamb_step(ws, grads, avgs, sqs, group["lr"], b1, b2,
                                   group["eps"], group["weight_decay"], step,
-                                  group["bias_correction"], adapt, coef)
+                                  group["bias_correction"], adapt, coef,
+                                  models)
 
-    def _eager_update(self, p, group, clip):
+    def _eager_update(self, p, w, g, group):
+        """w: the tensor to update (p, or its fp32 master); g: the dense,
+        clipped gradient in w's dtype."""
         b1, b2 = group["betas"]
-        g = self._eager_grad(p, clip)
         step, m, v = self._moments(p)
         m.mul_(b1).add_(g, alpha=1 - b1)
         v.mul_(b2).addcmul_(g, g, value=1 - b2)
@@ -66,16 +74,16 @@ class FusedLAMB(FusedMomentOptimizer):
             bc1 = 1 - b1 ** step
             bc2 = 1 - b2 ** step
         # 16-bit parameters: u and the two norms in fp32
-        acc = p.dtype if p.dtype in (torch.float32, torch.float64) \
+        acc = w.dtype if w.dtype in (torch.float32, torch.float64) \
             else torch.float32
-        w = p.to(acc)
+        wa = w.to(acc)
         u = (m.to(acc) / bc1) / ((v.to(acc) / bc2).sqrt_().add_(group["eps"]))
-        u.add_(w, alpha=group["weight_decay"])
+        u.add_(wa, alpha=group["weight_decay"])
         if group["weight_decay"] != 0 or group["always_adapt"]:
-            w_norm = torch.linalg.vector_norm(w)
+            w_norm = torch.linalg.vector_norm(wa)
             u_norm = torch.linalg.vector_norm(u)
             # 0-dim tensors, no host read; the compares are false for NaN
             trust = torch.where((w_norm > 0) & (u_norm > 0),
                                 w_norm / u_norm, torch.ones_like(w_norm))
             u.mul_(trust)
-        p.sub_(u.to(p.dtype), alpha=group["lr"])
+        w.sub_(u.to(w.dtype), alpha=group["lr"])

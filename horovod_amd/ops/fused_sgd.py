@@ -6,9 +6,16 @@ launches per ResNet-50 step); FusedSGD issues ceil(161/48) = 4.  Combine
 with hvd.DistributedOptimizer exactly like torch.optim.SGD.
 
 NOTE: the fused kernel path covers CUDA fp32 parameters with a dense
-gradient only.  CPU or non-fp32 params (e.g. bf16 master weights) and sparse
-gradients take a correct eager fallback and a one-time warning is emitted so
-a benchmarked configuration cannot silently lose the fusion.
+gradient and, with master_weights=True, CUDA fp16/bf16 parameters with a
+dense gradient of their own dtype.  Other parameters (CPU, sparse gradients,
+fp16/bf16 without master_weights) take a correct eager fallback and a
+one-time warning is emitted so a benchmarked configuration cannot silently
+lose the fusion.
+
+master_weights=True keeps an fp32 `master_param` and an fp32
+`momentum_buffer` for every fp16/bf16 parameter; the kernel updates the
+master and writes it, rounded to nearest-even, into the parameter in the same
+pass (see _fused_base.py).
 
 max_grad_norm=<float> clips by the global L2 norm of all gradients inside
 step(): one native multi-tensor norm pass (csrc/clip_kernels.hip), then the
@@ -23,38 +30,44 @@ from horovod_amd.ops._fused_base import FusedOptimizer
 
 class FusedSGD(FusedOptimizer):
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0,
-                 dampening=0.0, nesterov=False, max_grad_norm=None):
+                 dampening=0.0, nesterov=False, max_grad_norm=None,
+                 master_weights=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("nesterov requires momentum > 0, dampening 0")
         super().__init__(params, dict(
             lr=lr, momentum=momentum, weight_decay=weight_decay,
             dampening=dampening, nesterov=nesterov,
-            max_grad_norm=max_grad_norm))
+            max_grad_norm=max_grad_norm, master_weights=master_weights))
 
-    def _fused_update(self, params, group, coef):
+    def _fused_update(self, params, group, coef, master):
         momenta = []
         if group["momentum"] != 0:
             for p in params:
                 st = self.state[p]
                 if st.get("momentum_buffer") is None:
-                    st["momentum_buffer"] = torch.zeros_like(p)
+                    st["momentum_buffer"] = torch.zeros_like(
+                        p, dtype=torch.float32)
                 momenta.append(st["momentum_buffer"])
-        _core.fused_sgd_step(params, [p.grad for p in params], momenta,
+        ws = [self.state[p]["master_param"] for p in params] if master \
+            else params
+        _core.fused_sgd_step(ws, [p.grad for p in params], momenta,
                              group["lr"], group["momentum"],
                              group["weight_decay"], group["dampening"],
-                             group["nesterov"], coef)
+                             group["nesterov"], coef,
+                             params if master else None)
 
-    def _eager_update(self, p, group, clip):
-        g = self._eager_grad(p, clip)
+    def _eager_update(self, p, w, g, group):
+        """w: the tensor to update (p, or its fp32 master); g: the dense,
+        clipped gradient in w's dtype."""
         if group["weight_decay"]:
-            g = g.add(p, alpha=group["weight_decay"])
+            g = g.add(w, alpha=group["weight_decay"])
         if group["momentum"]:
             st = self.state[p]
             buf = st.get("momentum_buffer")
             if buf is None:
                 # in p's layout, so that a later step can take the kernel
-                buf = st["momentum_buffer"] = torch.empty_like(p).copy_(g)
+                buf = st["momentum_buffer"] = torch.empty_like(w).copy_(g)
             else:
                 buf.mul_(group["momentum"]).add_(g, alpha=1 - group["dampening"])
             g = g.add(buf, alpha=group["momentum"]) if group["nesterov"] else buf
-        p.add_(g, alpha=-group["lr"])
+        w.add_(g, alpha=-group["lr"])
