@@ -32,10 +32,13 @@ template <typename LP, bool HAS_COEF>
 __global__ __launch_bounds__(256) void fused_adamw_k(
     AdamwArgsOf<LP> args, int blocks_per, float lr, float beta1, float beta2,
     float eps, float weight_decay, float step_size, float inv_bc2_sqrt,
-    const float* __restrict__ grad_coef) {
+    const float* __restrict__ grad_coef, const float* __restrict__ skip) {
   using G = typename LowPrec<LP>::Grad;
   constexpr bool MODEL = LowPrec<LP>::kModel;
   constexpr int W = LowPrec<LP>::kVec;
+  // one uniform load: a set flag (an overflowed step) leaves every row as
+  // it is
+  if (skip && *skip != 0.0f) return;
   int t = blockIdx.x / blocks_per;
   if (t >= args.count) return;
   // one uniform load; the gradient tensors are never written
@@ -87,7 +90,7 @@ template <typename LP>
 hipError_t launch_adamw(const AdamwArgsOf<LP>& args, float lr, float beta1,
                         float beta2, float eps, float weight_decay,
                         long long step, const float* grad_coef,
-                        hipStream_t stream) {
+                        const float* skip, hipStream_t stream) {
   if (args.count == 0) return hipSuccess;
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
@@ -98,7 +101,7 @@ hipError_t launch_adamw(const AdamwArgsOf<LP>& args, float lr, float beta1,
   auto kernel = grad_coef ? fused_adamw_k<LP, true> : fused_adamw_k<LP, false>;
   kernel<<<grid, block, 0, stream>>>(args, bpc, lr, beta1, beta2, eps,
                                      weight_decay, step_size, inv_bc2_sqrt,
-                                     grad_coef);
+                                     grad_coef, skip);
   return hipGetLastError();
 }
 
@@ -107,24 +110,24 @@ hipError_t launch_adamw(const AdamwArgsOf<LP>& args, float lr, float beta1,
 hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             float beta2, float eps, float weight_decay,
                             long long step, const float* grad_coef,
-                            hipStream_t stream) {
+                            const float* skip, hipStream_t stream) {
   return launch_adamw<void>(args, lr, beta1, beta2, eps, weight_decay, step,
-                            grad_coef, stream);
+                            grad_coef, skip, stream);
 }
 
 hipError_t FusedAdamwMasterLaunch(const AdamwMasterBatchArgs& args, int dt,
                                   float lr, float beta1, float beta2,
                                   float eps, float weight_decay,
                                   long long step, const float* grad_coef,
-                                  hipStream_t stream) {
+                                  const float* skip, hipStream_t stream) {
   switch (dt) {
     case DT_F16:
       return launch_adamw<__half>(args, lr, beta1, beta2, eps, weight_decay,
-                                  step, grad_coef, stream);
+                                  step, grad_coef, skip, stream);
     case DT_BF16:
       return launch_adamw<__hip_bfloat16>(args, lr, beta1, beta2, eps,
                                           weight_decay, step, grad_coef,
-                                          stream);
+                                          skip, stream);
     default:
       return hipErrorInvalidValue;
   }

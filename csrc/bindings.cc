@@ -136,6 +136,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return hvd::gpu::MultiTensorGradNorm(grads, max_norm);
         },
         py::arg("grads"), py::arg("max_norm"));
+  auto opt_tensor = [](const py::object& o) {
+    return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
+  };
+  // the norm pass of a loss-scaled step -> {total_norm, coef, found, scale}
+  m.def("multi_tensor_scaled_grad_norm",
+        [opt_tensor](std::vector<at::Tensor> grads,
+                     std::optional<double> max_norm, py::object scale,
+                     py::object found_inf, py::object growth_tracker,
+                     double growth_factor, double backoff_factor,
+                     int64_t growth_interval) {
+          return hvd::gpu::MultiTensorScaledGradNorm(
+              grads, max_norm, opt_tensor(scale), opt_tensor(found_inf),
+              opt_tensor(growth_tracker), growth_factor, backoff_factor,
+              growth_interval);
+        },
+        py::arg("grads"), py::arg("max_norm") = py::none(),
+        py::arg("scale") = py::none(), py::arg("found_inf") = py::none(),
+        py::arg("growth_tracker") = py::none(),
+        py::arg("growth_factor") = 1.0, py::arg("backoff_factor") = 1.0,
+        py::arg("growth_interval") = 0);
   m.def("multi_tensor_scale_",
         [](std::vector<at::Tensor> tensors, at::Tensor coef) {
           hvd::gpu::MultiTensorScale(tensors, coef);
@@ -143,10 +163,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tensors"), py::arg("coef"));
 
   // ---- fused optimizer kernels (grad_coef: None or a 1-element fp32
-  // device tensor, e.g. multi_tensor_grad_norm(...)[1:2]) -------------------
-  auto opt_tensor = [](const py::object& o) {
-    return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
-  };
+  // device tensor, e.g. multi_tensor_grad_norm(...)[1:2]; skip: None or such
+  // a tensor that, nonzero, turns the call into a no-op on the device, e.g.
+  // multi_tensor_scaled_grad_norm(...)[2:3]) --------------------------------
   // model_params: None, or the fp16/bf16 model parameters of a master-weight
   // step (params are then their fp32 masters)
   using OptTensors = std::optional<std::vector<at::Tensor>>;
@@ -157,17 +176,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                      std::vector<at::Tensor> momenta, double lr,
                      double momentum, double weight_decay, double dampening,
                      bool nesterov, py::object grad_coef,
-                     OptTensors model_params) {
+                     OptTensors model_params, py::object skip) {
           hvd::gpu::FusedSgdStep(params, grads, momenta, lr, momentum,
                                  weight_decay, dampening, nesterov,
                                  opt_tensor(grad_coef),
-                                 opt_list(model_params));
+                                 opt_list(model_params), opt_tensor(skip));
         },
         py::arg("params"), py::arg("grads"), py::arg("momenta"),
         py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
         py::arg("dampening"), py::arg("nesterov"),
         py::arg("grad_coef") = py::none(),
-        py::arg("model_params") = py::none());
+        py::arg("model_params") = py::none(), py::arg("skip") = py::none());
 
   m.def("fused_adamw_step",
         [opt_tensor, opt_list](std::vector<at::Tensor> params,
@@ -176,17 +195,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                      std::vector<at::Tensor> exp_avg_sqs, double lr,
                      double beta1, double beta2, double eps,
                      double weight_decay, int64_t step,
-                     py::object grad_coef, OptTensors model_params) {
+                     py::object grad_coef, OptTensors model_params,
+                     py::object skip) {
           hvd::gpu::FusedAdamwStep(params, grads, exp_avgs, exp_avg_sqs, lr,
                                    beta1, beta2, eps, weight_decay, step,
                                    opt_tensor(grad_coef),
-                                   opt_list(model_params));
+                                   opt_list(model_params), opt_tensor(skip));
         },
         py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
         py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("step"), py::arg("grad_coef") = py::none(),
-        py::arg("model_params") = py::none());
+        py::arg("model_params") = py::none(), py::arg("skip") = py::none());
 
   m.def("fused_lamb_step",
         [opt_tensor, opt_list](std::vector<at::Tensor> params,
@@ -196,19 +216,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                      double beta1, double beta2, double eps,
                      double weight_decay, int64_t step, bool bias_correction,
                      bool adapt, py::object grad_coef,
-                     OptTensors model_params) {
+                     OptTensors model_params, py::object skip) {
           return hvd::gpu::FusedLambStep(params, grads, exp_avgs, exp_avg_sqs,
                                          lr, beta1, beta2, eps, weight_decay,
                                          step, bias_correction, adapt,
                                          opt_tensor(grad_coef),
-                                         opt_list(model_params));
+                                         opt_list(model_params),
+                                         opt_tensor(skip));
         },
         py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
         py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("step"), py::arg("bias_correction"), py::arg("adapt"),
         py::arg("grad_coef") = py::none(),
-        py::arg("model_params") = py::none());
+        py::arg("model_params") = py::none(), py::arg("skip") = py::none());
 
   m.def("fused_bn_relu_forward",
         [](at::Tensor x, py::object residual, at::Tensor gamma, at::Tensor beta,

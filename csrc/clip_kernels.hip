@@ -1,6 +1,8 @@
 // Global-norm gradient clipping for CDNA4: a multi-tensor squared-norm pass,
 // a one-block finalize that turns the block partials into {total_norm, coef},
-// and an in-place multi-tensor scale that reads coef from device memory.
+// and an in-place multi-tensor scale that reads coef from device memory.  A
+// second finalize serves loss scaling: it also unscales, flags an overflow
+// and updates the scale on the device (scaled_clip_finalize_k).
 //
 // Work is divided by elements, not by tensor: every block owns one fixed
 // kChunkElems-element chunk of one tensor and finds its tensor by searching
@@ -89,6 +91,59 @@ __global__ __launch_bounds__(kFinalizeThreads) void clip_finalize_k(
   }
 }
 
+// clip_finalize_k for a loss-scaled step (ScaledFinalizeParams, kernels.h):
+// the same sum in the same order, then {total_norm, coef, found, S} and the
+// scale update, all by thread 0.  A non-finite sum of squares is the overflow
+// test: every inf or NaN element makes it so, and so do finite gradients
+// whose norm passes sqrt(FLT_MAX) ~ 1.8e19 -- for a loss scaler also "scale
+// too high".  The scale is read before it is updated: out[3] and coef belong
+// to the gradients at hand.
+__global__ __launch_bounds__(kFinalizeThreads) void scaled_clip_finalize_k(
+    const float* __restrict__ partials, long long n, ScaledFinalizeParams p,
+    float* __restrict__ out) {
+  __shared__ double part[kFinalizeThreads];
+  double s = 0.0;
+  for (long long i = threadIdx.x; i < n; i += kFinalizeThreads)
+    s += (double)partials[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int half = kFinalizeThreads / 2; half > 0; half >>= 1) {
+    if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double sum = part[0];
+  const float scale = p.scale ? *p.scale : 1.0f;
+  // x - x is 0 for finite x and NaN for inf and NaN
+  bool found = !(sum - sum == 0.0);
+  if (p.found_inf && *p.found_inf != 0.0f) found = true;
+  const float inv = 1.0f / scale;
+  const float total_norm = (float)sqrt(sum) * inv;
+  float clip = 1.0f;
+  if (p.has_max_norm) {
+    clip = (1.0f / (total_norm + 1e-6f)) * p.max_norm;
+    if (clip > 1.0f) clip = 1.0f;  // a compare: NaN stays NaN
+  }
+  out[0] = total_norm;
+  out[1] = clip * inv;
+  out[2] = found ? 1.0f : 0.0f;
+  out[3] = scale;
+  if (!p.growth_tracker) return;
+  if (found) {
+    *p.scale = scale * p.backoff_factor;
+    *p.growth_tracker = 0;
+    return;
+  }
+  const int successive = *p.growth_tracker + 1;
+  if (successive == p.growth_interval) {
+    const float grown = scale * p.growth_factor;
+    if (grown - grown == 0.0f) *p.scale = grown;
+    *p.growth_tracker = 0;
+  } else {
+    *p.growth_tracker = successive;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kChunkThreads) void multi_scale_k(
     ClipBatchArgs args, const float* __restrict__ coef_ptr) {
@@ -148,6 +203,16 @@ hipError_t ClipFinalizeLaunch(const float* partials, long long n_partials,
                               hipStream_t stream) {
   clip_finalize_k<<<dim3(1), dim3(kFinalizeThreads), 0, stream>>>(
       partials, n_partials, max_norm, out);
+  return hipGetLastError();
+}
+
+hipError_t ScaledClipFinalizeLaunch(const float* partials,
+                                    long long n_partials,
+                                    const ScaledFinalizeParams& p, float* out,
+                                    hipStream_t stream) {
+  if (p.growth_tracker && !p.scale) return hipErrorInvalidValue;
+  scaled_clip_finalize_k<<<dim3(1), dim3(kFinalizeThreads), 0, stream>>>(
+      partials, n_partials, p, out);
   return hipGetLastError();
 }
 

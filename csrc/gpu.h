@@ -9,6 +9,7 @@
 #pragma once
 
 #include <cstdint>
+#include <optional>
 #include <vector>
 
 #include <ATen/ATen.h>
@@ -95,6 +96,23 @@ at::Tensor SyncBnBackwardApply(at::Tensor x, at::Tensor dy, at::Tensor mean,
 // hence coef 1 by that formula unless max_norm < 1e-6.
 at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
                                double max_norm);
+// The norm pass of a loss-scaled step (scaled_clip_finalize_k): the same
+// multi-tensor pass over gradients that still carry the loss scale S, then
+// -> fp32 [4] = {total_norm, coef, found, S}.  S = *scale (1 without one);
+// total_norm is the unscaled norm; coef = clip / S with clip the coefficient
+// above for the unscaled norm (1 without max_norm), i.e. what a step kernel
+// multiplies the scaled gradient by; found = 1 when the sum of squares is not
+// finite or *found_inf is nonzero, else 0, in the form the steps take as
+// `skip`.  With growth_tracker, *scale and the tracker are then updated in
+// place by the rule of torch._amp_update_scale_.  scale, found_inf: undefined
+// or 1-element fp32 tensors on the gradients' device; growth_tracker:
+// undefined or 1-element int32, and needs a scale.  Everything is checked
+// before the first launch.
+at::Tensor MultiTensorScaledGradNorm(
+    std::vector<at::Tensor>& grads, std::optional<double> max_norm,
+    at::Tensor scale = at::Tensor(), at::Tensor found_inf = at::Tensor(),
+    at::Tensor growth_tracker = at::Tensor(), double growth_factor = 1.0,
+    double backoff_factor = 1.0, int64_t growth_interval = 0);
 // tensors[i] *= coef in place; coef is a 1-element fp32 device tensor.
 void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef);
 
@@ -113,12 +131,18 @@ void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef);
 // within a call; each takes launches of its own), every tuple has one size,
 // device and layout, and the kernels write the updated master, rounded to
 // nearest-even, into the model parameter.
+//
+// skip (all three steps): undefined, or a 1-element fp32 device tensor.  When
+// it is nonzero the kernels return without touching any tensor (and the LAMB
+// trust ratios are all 1); the host does not learn of it.  Undefined or zero
+// gives the results of a call without it, bit for bit.
 void FusedSgdStep(std::vector<at::Tensor>& params,
                   std::vector<at::Tensor>& grads,
                   std::vector<at::Tensor>& momenta, double lr, double momentum,
                   double weight_decay, double dampening, bool nesterov,
                   at::Tensor grad_coef = at::Tensor(),
-                  const std::vector<at::Tensor>* model_params = nullptr);
+                  const std::vector<at::Tensor>* model_params = nullptr,
+                  at::Tensor skip = at::Tensor());
 
 // Fused AdamW step (decoupled weight decay, torch.optim.AdamW math);
 // step is the 1-based step count for bias correction.  grad_coef as in
@@ -130,7 +154,8 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
                     double beta1, double beta2, double eps,
                     double weight_decay, int64_t step,
                     at::Tensor grad_coef = at::Tensor(),
-                    const std::vector<at::Tensor>* model_params = nullptr);
+                    const std::vector<at::Tensor>* model_params = nullptr,
+                    at::Tensor skip = at::Tensor());
 
 // Fused LAMB step (lamb_kernels.hip): AdamW's moments, then per tensor
 // p -= lr * trust * u with u = mhat / (sqrt(vhat) + eps) + weight_decay * p
@@ -148,7 +173,8 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                          double weight_decay, int64_t step,
                          bool bias_correction, bool adapt,
                          at::Tensor grad_coef = at::Tensor(),
-                         const std::vector<at::Tensor>* model_params = nullptr);
+                         const std::vector<at::Tensor>* model_params = nullptr,
+                         at::Tensor skip = at::Tensor());
 
 }  // namespace gpu
 }  // namespace hvd

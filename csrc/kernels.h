@@ -158,11 +158,16 @@ static_assert(sizeof(SgdMasterBatchArgs) == 1928 &&
 
 // ---- Fused SGD (sgd_kernels.hip) ------------------------------------------
 // grad_coef: null, or a device fp32 scalar every gradient element is
-// multiplied by (the global-norm clip coefficient) before weight decay and
-// momentum; the gradients themselves are only read.
+// multiplied by (the global-norm clip coefficient, the reciprocal of a loss
+// scale, or their product) before weight decay and momentum; the gradients
+// themselves are only read.
+// skip (every optimizer launch): null, or a device fp32 flag.  Nonzero, the
+// whole grid returns after one uniform load and no row is touched; null or
+// zero changes nothing in the arithmetic.
 hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
                           float weight_decay, float dampening, bool nesterov,
-                          const float* grad_coef, hipStream_t stream);
+                          const float* grad_coef, const float* skip,
+                          hipStream_t stream);
 // Master weights: the same kernel instantiated for dt in {DT_F16, DT_BF16}.
 // kRowParam holds the fp32 master, kRowGrad a gradient of type dt (widened
 // exactly as it is read), kRowSgdModel the model parameter of type dt, which
@@ -170,7 +175,8 @@ hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
 hipError_t FusedSgdMasterLaunch(const SgdMasterBatchArgs& args, int dt,
                                 float lr, float momentum, float weight_decay,
                                 float dampening, bool nesterov,
-                                const float* grad_coef, hipStream_t stream);
+                                const float* grad_coef, const float* skip,
+                                hipStream_t stream);
 
 // ---- Fused AdamW (adamw_kernels.hip) --------------------------------------
 // step is 1-based (bias correction uses beta^step).  grad_coef as in
@@ -178,13 +184,13 @@ hipError_t FusedSgdMasterLaunch(const SgdMasterBatchArgs& args, int dt,
 hipError_t FusedAdamwLaunch(const AdamwBatchArgs& args, float lr, float beta1,
                             float beta2, float eps, float weight_decay,
                             long long step, const float* grad_coef,
-                            hipStream_t stream);
+                            const float* skip, hipStream_t stream);
 // Master weights, as FusedSgdMasterLaunch; the model parameter is kRowModel.
 hipError_t FusedAdamwMasterLaunch(const AdamwMasterBatchArgs& args, int dt,
                                   float lr, float beta1, float beta2,
                                   float eps, float weight_decay,
                                   long long step, const float* grad_coef,
-                                  hipStream_t stream);
+                                  const float* skip, hipStream_t stream);
 
 // ---- Global-norm gradient clipping (clip_kernels.hip) ----------------------
 // Chunked.  One row; tensors are dense, of one dtype per launch (dt in
@@ -201,6 +207,35 @@ hipError_t MultiSqNormLaunch(const ClipBatchArgs& args, int dt,
 // 1), i.e. 1 unless max_norm < 1e-6.
 hipError_t ClipFinalizeLaunch(const float* partials, long long n_partials,
                               float max_norm, float* out, hipStream_t stream);
+// The finalize of a loss-scaled step.  Sums the partials exactly as
+// ClipFinalizeLaunch does and writes out[4] = {total_norm, coef, found, S}:
+//   S          = *p.scale (1 without one): the scale the gradients carry
+//   found      = 1 if the fp64 sum is not finite (an inf or NaN element, or
+//                finite gradients whose norm passes ~1.8e19) or *p.found_inf
+//                is nonzero, else 0
+//   total_norm = (float)sqrt(sum) * (1.0f / S), the unscaled norm
+//   coef       = clip * (1.0f / S), clip = min(max_norm / (total_norm +
+//                1e-6), 1) by ClipFinalizeLaunch's arithmetic, or 1 without
+//                has_max_norm
+// and then, with p.growth_tracker, updates *p.scale and the tracker in place
+// by the rule of torch._amp_update_scale_: on found scale *= backoff and
+// tracker = 0; else tracker += 1, and once it is growth_interval, scale *=
+// growth if that is finite, and tracker = 0.
+struct ScaledFinalizeParams {
+  bool has_max_norm = false;
+  float max_norm = 0.0f;
+  float* scale = nullptr;            // device, 1 element; written only
+                                     // with growth_tracker
+  const float* found_inf = nullptr;  // device, 1 element
+  int* growth_tracker = nullptr;     // device, 1 element; needs scale
+  float growth_factor = 1.0f;
+  float backoff_factor = 1.0f;
+  int growth_interval = 0;
+};
+hipError_t ScaledClipFinalizeLaunch(const float* partials,
+                                    long long n_partials,
+                                    const ScaledFinalizeParams& p, float* out,
+                                    hipStream_t stream);
 // x *= *coef in place; the whole grid returns without touching memory when
 // *coef == 1 (but not when it is NaN).
 hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
@@ -217,6 +252,8 @@ hipError_t MultiScaleLaunch(const ClipBatchArgs& args, int dt,
 //      trust[out_index[t]] = |p| / |u| if adapt and both norms are > 0
 //      (false for NaN), else 1
 //   3. update: p -= lr * trust[out_index[t]] * u, u recomputed from m, v
+// With a set skip flag 1. and 3. touch nothing and 2. writes a ratio of 1 for
+// each of its tensors without reading the partials.
 
 // Bias correction folded on the host: mhat = m * inv_bc1, sqrt(vhat) =
 // sqrt(v) * inv_bc2_sqrt (both 1 without bias correction).
@@ -230,26 +267,29 @@ LambScalars LambFoldScalars(float lr, float beta1, float beta2, float eps,
                             float weight_decay, long long step,
                             bool bias_correction);
 hipError_t LambMomentsLaunch(const LambBatchArgs& args, const LambScalars& s,
-                             const float* grad_coef, float* partials,
-                             hipStream_t stream);
+                             const float* grad_coef, const float* skip,
+                             float* partials, hipStream_t stream);
 hipError_t LambTrustLaunch(const LambBatchArgs& args, const float* partials,
-                           bool adapt, float* trust, hipStream_t stream);
+                           bool adapt, const float* skip, float* trust,
+                           hipStream_t stream);
 hipError_t LambUpdateLaunch(const LambBatchArgs& args, const LambScalars& s,
-                            const float* trust, hipStream_t stream);
+                            const float* trust, const float* skip,
+                            hipStream_t stream);
 // Master weights (dt in {DT_F16, DT_BF16}, one per launch): pass 1 reads the
 // fp32 master and a gradient of type dt, so norms and trust ratios are the
 // master's; pass 3 writes the master and, rounded to nearest-even, the model
 // parameter of type dt in kRowModel.
 hipError_t LambMomentsMasterLaunch(const LambMasterBatchArgs& args, int dt,
                                    const LambScalars& s,
-                                   const float* grad_coef, float* partials,
-                                   hipStream_t stream);
+                                   const float* grad_coef, const float* skip,
+                                   float* partials, hipStream_t stream);
 hipError_t LambTrustLaunch(const LambMasterBatchArgs& args,
-                           const float* partials, bool adapt, float* trust,
+                           const float* partials, bool adapt,
+                           const float* skip, float* trust,
                            hipStream_t stream);
 hipError_t LambUpdateMasterLaunch(const LambMasterBatchArgs& args, int dt,
                                   const LambScalars& s, const float* trust,
-                                  hipStream_t stream);
+                                  const float* skip, hipStream_t stream);
 
 // ---- Fused BatchNorm(+Add)+ReLU (bn_kernels.hip) --------------------------
 // NHWC dense activations [total=N*H*W rows, C channels], C % 8 == 0,

@@ -49,9 +49,12 @@ using LambArgsOf = typename std::conditional<LowPrec<LP>::kModel,
 template <typename LP, bool HAS_COEF>
 __global__ __launch_bounds__(kChunkThreads) void lamb_moments_k(
     LambArgsOf<LP> args, LambScalars s, const float* __restrict__ grad_coef,
-    float* __restrict__ partials) {
+    const float* __restrict__ skip, float* __restrict__ partials) {
   using G = typename LowPrec<LP>::Grad;
   constexpr int W = LowPrec<LP>::kVec;
+  // one uniform load: a set flag (an overflowed step) leaves the moments as
+  // they are and the partials unwritten (lamb_trust_k does not read them)
+  if (skip && *skip != 0.0f) return;
   const ChunkRef c = find_chunk(args);
   // one uniform load; the gradient tensors are never written
   const float coef = HAS_COEF ? *grad_coef : 1.0f;
@@ -104,10 +107,15 @@ __global__ __launch_bounds__(kChunkThreads) void lamb_moments_k(
 template <typename Args>
 __global__ __launch_bounds__(kTrustThreads) void lamb_trust_k(
     Args args, const float* __restrict__ partials, bool adapt,
-    float* __restrict__ trust) {
+    const float* __restrict__ skip, float* __restrict__ trust) {
   __shared__ double part_p[kTrustThreads];
   __shared__ double part_u[kTrustThreads];
   const int t = blockIdx.x;
+  // a skipped step wrote no partials: the ratio is defined as 1
+  if (skip && *skip != 0.0f) {
+    if (threadIdx.x == 0) trust[args.out_index[t]] = 1.0f;
+    return;
+  }
   const unsigned int first = args.block_prefix[t];
   const unsigned int n = args.block_prefix[t + 1] - first;
   const float* __restrict__ slots = partials + 2 * (args.partial_base + first);
@@ -139,10 +147,12 @@ __global__ __launch_bounds__(kTrustThreads) void lamb_trust_k(
 // With LP the updated master also goes to the model parameter, rounded.
 template <typename LP>
 __global__ __launch_bounds__(kChunkThreads) void lamb_update_k(
-    LambArgsOf<LP> args, LambScalars s, const float* __restrict__ trust) {
+    LambArgsOf<LP> args, LambScalars s, const float* __restrict__ trust,
+    const float* __restrict__ skip) {
   using Q = typename LowPrec<LP>::Grad;
   constexpr bool MODEL = LowPrec<LP>::kModel;
   constexpr int W = LowPrec<LP>::kVec;
+  if (skip && *skip != 0.0f) return;  // as lamb_moments_k
   const ChunkRef c = find_chunk(args);
   const float step = s.lr * trust[args.out_index[c.tensor]];
   float* __restrict__ p = (float*)args.ptr[kRowParam][c.tensor];
@@ -177,31 +187,32 @@ __global__ __launch_bounds__(kChunkThreads) void lamb_update_k(
 
 template <typename LP>
 hipError_t launch_moments(const LambArgsOf<LP>& args, const LambScalars& s,
-                          const float* grad_coef, float* partials,
-                          hipStream_t stream) {
+                          const float* grad_coef, const float* skip,
+                          float* partials, hipStream_t stream) {
   if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
   dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
   auto kernel =
       grad_coef ? lamb_moments_k<LP, true> : lamb_moments_k<LP, false>;
-  kernel<<<grid, block, 0, stream>>>(args, s, grad_coef, partials);
+  kernel<<<grid, block, 0, stream>>>(args, s, grad_coef, skip, partials);
   return hipGetLastError();
 }
 
 template <typename Args>
 hipError_t launch_trust(const Args& args, const float* partials, bool adapt,
-                        float* trust, hipStream_t stream) {
+                        const float* skip, float* trust, hipStream_t stream) {
   if (args.count == 0) return hipSuccess;
   lamb_trust_k<Args><<<dim3(args.count), dim3(kTrustThreads), 0, stream>>>(
-      args, partials, adapt, trust);
+      args, partials, adapt, skip, trust);
   return hipGetLastError();
 }
 
 template <typename LP>
 hipError_t launch_update(const LambArgsOf<LP>& args, const LambScalars& s,
-                         const float* trust, hipStream_t stream) {
+                         const float* trust, const float* skip,
+                         hipStream_t stream) {
   if (args.count == 0 || args.block_prefix[args.count] == 0) return hipSuccess;
   dim3 grid(args.block_prefix[args.count]), block(kChunkThreads);
-  lamb_update_k<LP><<<grid, block, 0, stream>>>(args, s, trust);
+  lamb_update_k<LP><<<grid, block, 0, stream>>>(args, s, trust, skip);
   return hipGetLastError();
 }
 
@@ -228,50 +239,54 @@ LambScalars LambFoldScalars(float lr, float beta1, float beta2, float eps,
 }
 
 hipError_t LambMomentsLaunch(const LambBatchArgs& args, const LambScalars& s,
-                             const float* grad_coef, float* partials,
-                             hipStream_t stream) {
-  return launch_moments<void>(args, s, grad_coef, partials, stream);
+                             const float* grad_coef, const float* skip,
+                             float* partials, hipStream_t stream) {
+  return launch_moments<void>(args, s, grad_coef, skip, partials, stream);
 }
 
 hipError_t LambTrustLaunch(const LambBatchArgs& args, const float* partials,
-                           bool adapt, float* trust, hipStream_t stream) {
-  return launch_trust(args, partials, adapt, trust, stream);
+                           bool adapt, const float* skip, float* trust,
+                           hipStream_t stream) {
+  return launch_trust(args, partials, adapt, skip, trust, stream);
 }
 
 hipError_t LambUpdateLaunch(const LambBatchArgs& args, const LambScalars& s,
-                            const float* trust, hipStream_t stream) {
-  return launch_update<void>(args, s, trust, stream);
+                            const float* trust, const float* skip,
+                            hipStream_t stream) {
+  return launch_update<void>(args, s, trust, skip, stream);
 }
 
 hipError_t LambMomentsMasterLaunch(const LambMasterBatchArgs& args, int dt,
                                    const LambScalars& s,
-                                   const float* grad_coef, float* partials,
-                                   hipStream_t stream) {
+                                   const float* grad_coef, const float* skip,
+                                   float* partials, hipStream_t stream) {
   switch (dt) {
     case DT_F16:
-      return launch_moments<__half>(args, s, grad_coef, partials, stream);
+      return launch_moments<__half>(args, s, grad_coef, skip, partials,
+                                    stream);
     case DT_BF16:
-      return launch_moments<__hip_bfloat16>(args, s, grad_coef, partials,
-                                            stream);
+      return launch_moments<__hip_bfloat16>(args, s, grad_coef, skip,
+                                            partials, stream);
     default:
       return hipErrorInvalidValue;
   }
 }
 
 hipError_t LambTrustLaunch(const LambMasterBatchArgs& args,
-                           const float* partials, bool adapt, float* trust,
+                           const float* partials, bool adapt,
+                           const float* skip, float* trust,
                            hipStream_t stream) {
-  return launch_trust(args, partials, adapt, trust, stream);
+  return launch_trust(args, partials, adapt, skip, trust, stream);
 }
 
 hipError_t LambUpdateMasterLaunch(const LambMasterBatchArgs& args, int dt,
                                   const LambScalars& s, const float* trust,
-                                  hipStream_t stream) {
+                                  const float* skip, hipStream_t stream) {
   switch (dt) {
     case DT_F16:
-      return launch_update<__half>(args, s, trust, stream);
+      return launch_update<__half>(args, s, trust, skip, stream);
     case DT_BF16:
-      return launch_update<__hip_bfloat16>(args, s, trust, stream);
+      return launch_update<__hip_bfloat16>(args, s, trust, skip, stream);
     default:
       return hipErrorInvalidValue;
   }

@@ -25,15 +25,26 @@ using TensorList = std::vector<at::Tensor>;
 // Parallel lists: tensor i of list r goes to pointer row r of a descriptor.
 using Rows = std::vector<const TensorList*>;
 
-// Device pointer of an optional clip coefficient: undefined -> null.
-const float* GradCoefPtr(const at::Tensor& coef, int device) {
-  if (!coef.defined()) return nullptr;
-  if (!coef.is_cuda() || coef.get_device() != device ||
-      coef.scalar_type() != at::kFloat || coef.numel() != 1)
+// Device pointer of an optional 1-element device tensor of type T (a clip
+// coefficient, a skip flag, a loss scale, ...): undefined -> null.
+template <typename T = float>
+T* ScalarPtr(const at::Tensor& t, int device, const char* name,
+             const char* where = "parameters'") {
+  if (!t.defined()) return nullptr;
+  if (!t.is_cuda() || t.get_device() != device ||
+      t.scalar_type() != c10::CppTypeToScalarType<T>::value || t.numel() != 1)
     throw std::runtime_error(
-        "horovod_amd: grad_coef must be a 1-element fp32 tensor on the "
-        "parameters' device");
-  return coef.data_ptr<float>();
+        std::string("horovod_amd: ") + name + " must be a 1-element " +
+        (std::is_same<T, float>::value ? "fp32" : "int32") +
+        " tensor on the " + where + " device");
+  return t.data_ptr<T>();
+}
+
+const float* GradCoefPtr(const at::Tensor& coef, int device) {
+  return ScalarPtr(coef, device, "grad_coef");
+}
+const float* SkipPtr(const at::Tensor& skip, int device) {
+  return ScalarPtr(skip, device, "skip");
 }
 
 struct TupleInfo {
@@ -220,6 +231,54 @@ at::Tensor MultiTensorGradNorm(std::vector<at::Tensor>& grads,
   return out;
 }
 
+at::Tensor MultiTensorScaledGradNorm(std::vector<at::Tensor>& grads,
+                                     std::optional<double> max_norm,
+                                     at::Tensor scale, at::Tensor found_inf,
+                                     at::Tensor growth_tracker,
+                                     double growth_factor,
+                                     double backoff_factor,
+                                     int64_t growth_interval) {
+  // without gradients: the device of whichever tensor is given
+  int device = !grads.empty()        ? ClipDevice(grads[0])
+               : scale.defined()     ? ClipDevice(scale)
+               : found_inf.defined() ? ClipDevice(found_inf)
+                                     : (int)c10::hip::current_device();
+  ScaledFinalizeParams p;
+  p.has_max_norm = max_norm.has_value();
+  p.max_norm = (float)max_norm.value_or(0.0);
+  p.scale = ScalarPtr(scale, device, "scale", "gradients'");
+  p.found_inf = ScalarPtr(found_inf, device, "found_inf", "gradients'");
+  p.growth_tracker =
+      ScalarPtr<int>(growth_tracker, device, "growth_tracker", "gradients'");
+  p.growth_factor = (float)growth_factor;
+  p.backoff_factor = (float)backoff_factor;
+  if (p.growth_tracker && !p.scale)
+    throw std::runtime_error(
+        "horovod_amd: growth_tracker needs a scale to update");
+  if (growth_interval < 0 || growth_interval > INT32_MAX)
+    throw std::runtime_error("horovod_amd: growth_interval out of range");
+  p.growth_interval = (int)growth_interval;
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
+  int64_t total_blocks = 0;
+  for (const auto& g : grads) total_blocks += ChunkBlocks(g.numel());
+  // every slot is written by exactly one block before the finalize reads it
+  at::Tensor partials = at::empty({std::max<int64_t>(total_blocks, 1)}, f32);
+  at::Tensor out = at::empty({4}, f32);
+  unsigned long long base = 0;
+  // checks every gradient before its first launch
+  ForEachClipBatch(grads, device, [&](ClipBatchArgs& args, int dt) {
+    args.partial_base = base;
+    HIP_CHECK(MultiSqNormLaunch(args, dt, partials.data_ptr<float>(), stream));
+    base += args.block_prefix[args.count];
+  });
+  HIP_CHECK(ScaledClipFinalizeLaunch(partials.data_ptr<float>(),
+                                     (long long)base, p,
+                                     out.data_ptr<float>(), stream));
+  return out;
+}
+
 void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef) {
   if (tensors.empty()) return;
   int device = ClipDevice(tensors[0]);
@@ -237,7 +296,8 @@ void FusedSgdStep(std::vector<at::Tensor>& params,
                   std::vector<at::Tensor>& momenta, double lr, double momentum,
                   double weight_decay, double dampening, bool nesterov,
                   at::Tensor grad_coef,
-                  const std::vector<at::Tensor>* model_params) {
+                  const std::vector<at::Tensor>* model_params,
+                  at::Tensor skip) {
   // the kernel reads the momentum row exactly when the launcher sees a
   // nonzero fp32 momentum; without it `momenta` is not looked at
   const bool use_momentum = (float)momentum != 0.0f;
@@ -250,6 +310,7 @@ void FusedSgdStep(std::vector<at::Tensor>& params,
   c10::hip::HIPGuard guard(info.device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
   const float* coef = GradCoefPtr(grad_coef, info.device);
+  const float* skip_ptr = SkipPtr(skip, info.device);
   if (model_params) {
     rows = {&params, &grads, use_momentum ? &momenta : nullptr, model_params};
     ForEachMasterBatch<SgdMasterBatchArgs>(
@@ -257,14 +318,14 @@ void FusedSgdStep(std::vector<at::Tensor>& params,
           HIP_CHECK(FusedSgdMasterLaunch(args, dt, (float)lr, (float)momentum,
                                          (float)weight_decay,
                                          (float)dampening, nesterov, coef,
-                                         stream));
+                                         skip_ptr, stream));
         });
     return;
   }
   Batcher<SgdBatchArgs> batch([&](SgdBatchArgs& args) {
     HIP_CHECK(FusedSgdLaunch(args, (float)lr, (float)momentum,
                              (float)weight_decay, (float)dampening, nesterov,
-                             coef, stream));
+                             coef, skip_ptr, stream));
   });
   for (size_t i = 0; i < params.size(); ++i) batch.Add(rows, i);
   batch.Flush();
@@ -276,7 +337,8 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
                     std::vector<at::Tensor>& exp_avg_sqs, double lr,
                     double beta1, double beta2, double eps,
                     double weight_decay, int64_t step, at::Tensor grad_coef,
-                    const std::vector<at::Tensor>* model_params) {
+                    const std::vector<at::Tensor>* model_params,
+                    at::Tensor skip) {
   Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
   const TupleInfo info =
       CheckTuples("fused_adamw_step", "grads, exp_avgs and exp_avg_sqs", rows,
@@ -285,6 +347,7 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
   c10::hip::HIPGuard guard(info.device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
   const float* coef = GradCoefPtr(grad_coef, info.device);
+  const float* skip_ptr = SkipPtr(skip, info.device);
   if (model_params) {
     rows.push_back(model_params);
     ForEachMasterBatch<AdamwMasterBatchArgs>(
@@ -292,14 +355,14 @@ void FusedAdamwStep(std::vector<at::Tensor>& params,
           HIP_CHECK(FusedAdamwMasterLaunch(args, dt, (float)lr, (float)beta1,
                                            (float)beta2, (float)eps,
                                            (float)weight_decay, step, coef,
-                                           stream));
+                                           skip_ptr, stream));
         });
     return;
   }
   Batcher<AdamwBatchArgs> batch([&](AdamwBatchArgs& args) {
     HIP_CHECK(FusedAdamwLaunch(args, (float)lr, (float)beta1, (float)beta2,
                                (float)eps, (float)weight_decay, step, coef,
-                               stream));
+                               skip_ptr, stream));
   });
   for (size_t i = 0; i < params.size(); ++i) batch.Add(rows, i);
   batch.Flush();
@@ -313,7 +376,8 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                          double weight_decay, int64_t step,
                          bool bias_correction, bool adapt,
                          at::Tensor grad_coef,
-                         const std::vector<at::Tensor>* model_params) {
+                         const std::vector<at::Tensor>* model_params,
+                         at::Tensor skip) {
   Rows rows{&params, &grads, &exp_avgs, &exp_avg_sqs};
   const TupleInfo info =
       CheckTuples("fused_lamb_step", "grads, exp_avgs and exp_avg_sqs", rows,
@@ -324,6 +388,7 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
   c10::hip::HIPGuard guard(info.device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
   const float* coef = GradCoefPtr(grad_coef, info.device);
+  const float* skip_ptr = SkipPtr(skip, info.device);
   auto f32 =
       at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, info.device);
   // sized for the whole call; every slot is written by exactly one block
@@ -341,23 +406,26 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
     ForEachMasterBatch<LambMasterBatchArgs>(
         rows, true, [&](LambMasterBatchArgs& args, int dt) {
           args.partial_base = base;
-          HIP_CHECK(LambMomentsMasterLaunch(
-              args, dt, s, coef, partials.data_ptr<float>(), stream));
+          HIP_CHECK(LambMomentsMasterLaunch(args, dt, s, coef, skip_ptr,
+                                            partials.data_ptr<float>(),
+                                            stream));
           HIP_CHECK(LambTrustLaunch(args, partials.data_ptr<float>(), adapt,
-                                    trust.data_ptr<float>(), stream));
-          HIP_CHECK(LambUpdateMasterLaunch(args, dt, s,
-                                           trust.data_ptr<float>(), stream));
+                                    skip_ptr, trust.data_ptr<float>(),
+                                    stream));
+          HIP_CHECK(LambUpdateMasterLaunch(
+              args, dt, s, trust.data_ptr<float>(), skip_ptr, stream));
           base += args.block_prefix[args.count];
         });
     return trust;
   }
   Batcher<LambBatchArgs> batch([&](LambBatchArgs& args) {
     args.partial_base = base;
-    HIP_CHECK(LambMomentsLaunch(args, s, coef, partials.data_ptr<float>(),
-                                stream));
+    HIP_CHECK(LambMomentsLaunch(args, s, coef, skip_ptr,
+                                partials.data_ptr<float>(), stream));
     HIP_CHECK(LambTrustLaunch(args, partials.data_ptr<float>(), adapt,
-                              trust.data_ptr<float>(), stream));
-    HIP_CHECK(LambUpdateLaunch(args, s, trust.data_ptr<float>(), stream));
+                              skip_ptr, trust.data_ptr<float>(), stream));
+    HIP_CHECK(LambUpdateLaunch(args, s, trust.data_ptr<float>(), skip_ptr,
+                               stream));
     base += args.block_prefix[args.count];
   });
   for (int64_t i = 0; i < n; ++i) batch.Add(rows, (size_t)i, (unsigned int)i);

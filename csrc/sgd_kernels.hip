@@ -29,10 +29,13 @@ template <typename LP, bool NESTEROV, bool HAS_MOMENTUM, bool HAS_COEF>
 __global__ __launch_bounds__(256) void fused_sgd_k(
     SgdArgsOf<LP> args, int blocks_per, float lr, float momentum,
     float weight_decay, float dampening,
-    const float* __restrict__ grad_coef) {
+    const float* __restrict__ grad_coef, const float* __restrict__ skip) {
   using G = typename LowPrec<LP>::Grad;
   constexpr bool MODEL = LowPrec<LP>::kModel;
   constexpr int W = LowPrec<LP>::kVec;
+  // one uniform load: a set flag (an overflowed step) leaves every row as
+  // it is
+  if (skip && *skip != 0.0f) return;
   int t = blockIdx.x / blocks_per;
   if (t >= args.count) return;
   // one uniform load; the gradient tensors are never written
@@ -80,25 +83,27 @@ __global__ __launch_bounds__(256) void fused_sgd_k(
 template <typename LP, bool NESTEROV, bool HAS_MOMENTUM>
 void launch_sgd(const SgdArgsOf<LP>& args, float lr, float momentum,
                 float weight_decay, float dampening, const float* grad_coef,
-                hipStream_t stream) {
+                const float* skip, hipStream_t stream) {
   const int bpc = kBlocksPerTensor;
   dim3 grid(args.count * bpc), block(256);
   auto kernel = grad_coef ? fused_sgd_k<LP, NESTEROV, HAS_MOMENTUM, true>
                           : fused_sgd_k<LP, NESTEROV, HAS_MOMENTUM, false>;
   kernel<<<grid, block, 0, stream>>>(args, bpc, lr, momentum, weight_decay,
-                                     dampening, grad_coef);
+                                     dampening, grad_coef, skip);
 }
 
 template <typename LP>
 hipError_t launch_sgd_variant(const SgdArgsOf<LP>& args, float lr,
                               float momentum, float weight_decay,
                               float dampening, bool nesterov,
-                              const float* grad_coef, hipStream_t stream) {
+                              const float* grad_coef, const float* skip,
+                              hipStream_t stream) {
   if (args.count == 0) return hipSuccess;
   auto launch = momentum == 0.0f ? launch_sgd<LP, false, false>
                 : nesterov       ? launch_sgd<LP, true, true>
                                  : launch_sgd<LP, false, true>;
-  launch(args, lr, momentum, weight_decay, dampening, grad_coef, stream);
+  launch(args, lr, momentum, weight_decay, dampening, grad_coef, skip,
+         stream);
   return hipGetLastError();
 }
 
@@ -106,24 +111,27 @@ hipError_t launch_sgd_variant(const SgdArgsOf<LP>& args, float lr,
 
 hipError_t FusedSgdLaunch(const SgdBatchArgs& args, float lr, float momentum,
                           float weight_decay, float dampening, bool nesterov,
-                          const float* grad_coef, hipStream_t stream) {
+                          const float* grad_coef, const float* skip,
+                          hipStream_t stream) {
   return launch_sgd_variant<void>(args, lr, momentum, weight_decay, dampening,
-                                  nesterov, grad_coef, stream);
+                                  nesterov, grad_coef, skip, stream);
 }
 
 hipError_t FusedSgdMasterLaunch(const SgdMasterBatchArgs& args, int dt,
                                 float lr, float momentum, float weight_decay,
                                 float dampening, bool nesterov,
-                                const float* grad_coef, hipStream_t stream) {
+                                const float* grad_coef, const float* skip,
+                                hipStream_t stream) {
   switch (dt) {
     case DT_F16:
       return launch_sgd_variant<__half>(args, lr, momentum, weight_decay,
                                         dampening, nesterov, grad_coef,
-                                        stream);
+                                        skip, stream);
     case DT_BF16:
       return launch_sgd_variant<__hip_bfloat16>(args, lr, momentum,
                                                 weight_decay, dampening,
-                                                nesterov, grad_coef, stream);
+                                                nesterov, grad_coef, skip,
+                                                stream);
     default:
       return hipErrorInvalidValue;
   }

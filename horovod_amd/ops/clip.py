@@ -59,6 +59,22 @@ def group_max_grad_norm(param_groups):
     return values.pop() if values else None
 
 
+def torch_norm(grads, fp32=False):
+    """Global L2 norm of `grads` in torch ops, a 0-dim tensor on the device
+    of the first: the path of CPU, sparse or multi-device gradients.  `fp32`:
+    fp16/bf16 gradients are accumulated, and the norm returned, in fp32."""
+    if not grads:
+        return torch.zeros(())
+    first = grads[0].device
+    norms = []
+    for g in grads:
+        g = g.coalesce()._values() if g.is_sparse else g
+        wide = torch.float32 if fp32 and g.dtype in (
+            torch.float16, torch.bfloat16) else None
+        norms.append(torch.linalg.vector_norm(g, 2.0, dtype=wide).to(first))
+    return torch.linalg.vector_norm(torch.stack(norms), 2.0)
+
+
 class GradClip:
     """Pre-clip norm and clip coefficient of one optimizer step.
 
@@ -76,17 +92,10 @@ class GradClip:
         else:
             # CPU, sparse or multi-device gradients: same formula in torch ops
             coef = None
+            self.total_norm = torch_norm(grads)
             if grads:
-                first = grads[0].device
-                norms = [torch.linalg.vector_norm(
-                    g.coalesce()._values() if g.is_sparse else g, 2.0
-                ).to(first) for g in grads]
-                self.total_norm = torch.linalg.vector_norm(
-                    torch.stack(norms), 2.0)
                 coef = torch.clamp(max_norm / (self.total_norm + 1e-6),
                                    max=1.0)
-            else:
-                self.total_norm = torch.zeros(())
         self._coef = {} if coef is None else {coef.device: coef}
         self._first = coef
 

@@ -33,6 +33,13 @@ master_weights=True keeps an fp32 `master_param` and fp32 moments for every
 fp16/bf16 parameter.  p in the definition above is then the master: norms and
 trust ratios are the master's, and the last launch writes the master and,
 rounded to nearest-even, the parameter (see _fused_base.py).
+
+loss_scale="dynamic" (or a number for a static scale) makes the optimizer
+its own loss scaler for fp16 training: backward runs on
+`opt.scale_loss(loss)`; step() finds an overflow in one norm pass, unscales
+inside the moments kernel (g' above is then g * clip / scale) and skips the whole step on the device, without a
+host read before the update (see _fused_base.py and loss_scale.py).
+torch.amp.GradScaler.step(opt) is served by the same kernels.
 """
 import torch
 
@@ -46,13 +53,15 @@ class FusedLAMB(FusedMomentOptimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.01, bias_correction=True, always_adapt=False,
-                 max_grad_norm=None, master_weights=False):
+                 max_grad_norm=None, master_weights=False, loss_scale=None,
+                 loss_scale_args=None):
         super().__init__(params, dict(
             lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
             bias_correction=bias_correction, always_adapt=always_adapt,
-            max_grad_norm=max_grad_norm, master_weights=master_weights))
+            max_grad_norm=max_grad_norm, master_weights=master_weights,
+            loss_scale=loss_scale, loss_scale_args=loss_scale_args))
 
-    def _fused_update(self, params, group, coef, master):
+    def _fused_update(self, params, group, coef, master, skip):
         b1, b2 = group["betas"]
         adapt = group["weight_decay"] != 0 or group["always_adapt"]
         for step, ws, grads, avgs, sqs, models in self._by_step(params,
@@ -60,7 +69,7 @@ class FusedLAMB(FusedMomentOptimizer):
             _core.fused_lamb_step(ws, grads, avgs, sqs, group["lr"], b1, b2,
                                   group["eps"], group["weight_decay"], step,
                                   group["bias_correction"], adapt, coef,
-                                  models)
+                                  models, skip)
 
     def _eager_update(self, p, w, g, group):
         """w: the tensor to update (p, or its fp32 master); g: the dense,

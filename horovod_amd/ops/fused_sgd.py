@@ -21,6 +21,13 @@ max_grad_norm=<float> clips by the global L2 norm of all gradients inside
 step(): one native multi-tensor norm pass (csrc/clip_kernels.hip), then the
 step kernel multiplies each gradient by the coefficient as it reads it.
 p.grad is left unscaled; the pre-clip norm is kept in `last_grad_norm`.
+
+loss_scale="dynamic" (or a number for a static scale) makes the optimizer
+its own loss scaler for fp16 training: backward runs on
+`opt.scale_loss(loss)`; step() finds an overflow in one norm pass, unscales
+inside the step kernel and skips the whole step on the device, without a
+host read before the update (see _fused_base.py and loss_scale.py).
+torch.amp.GradScaler.step(opt) is served by the same kernels.
 """
 import torch
 
@@ -31,15 +38,17 @@ from horovod_amd.ops._fused_base import FusedOptimizer
 class FusedSGD(FusedOptimizer):
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0,
                  dampening=0.0, nesterov=False, max_grad_norm=None,
-                 master_weights=False):
+                 master_weights=False, loss_scale=None,
+                 loss_scale_args=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("nesterov requires momentum > 0, dampening 0")
         super().__init__(params, dict(
             lr=lr, momentum=momentum, weight_decay=weight_decay,
             dampening=dampening, nesterov=nesterov,
-            max_grad_norm=max_grad_norm, master_weights=master_weights))
+            max_grad_norm=max_grad_norm, master_weights=master_weights,
+            loss_scale=loss_scale, loss_scale_args=loss_scale_args))
 
-    def _fused_update(self, params, group, coef, master):
+    def _fused_update(self, params, group, coef, master, skip):
         momenta = []
         if group["momentum"] != 0:
             for p in params:
@@ -54,7 +63,7 @@ class FusedSGD(FusedOptimizer):
                              group["lr"], group["momentum"],
                              group["weight_decay"], group["dampening"],
                              group["nesterov"], coef,
-                             params if master else None)
+                             params if master else None, skip)
 
     def _eager_update(self, p, w, g, group):
         """w: the tensor to update (p, or its fp32 master); g: the dense,

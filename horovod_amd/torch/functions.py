@@ -79,7 +79,9 @@ def broadcast_optimizer_state(optimizer, root_rank, model=None,
                               process_set=global_process_set):
     """Broadcast an optimizer's state from root (reference:
     functions.py:74-199).  Tensor state entries are broadcast in place;
-    non-tensor entries (step counters, hyperparameters) travel via
+    non-tensor entries (step counters, hyperparameters, and the
+    "loss_scaler" entry of a fused optimizer with loss scaling: ranks with
+    different scales would add differently scaled gradients) travel via
     broadcast_object."""
     if isinstance(optimizer, torch.optim.LBFGS):
         raise ValueError("cannot broadcast torch.optim.LBFGS state")
@@ -113,16 +115,25 @@ def broadcast_optimizer_state(optimizer, root_rank, model=None,
             super(optimizer.__class__, optimizer).step()
         else:
             optimizer.step()
+        if "loss_scaler" in state_dict:
+            # that step is not one of the run's: it does not count as clean
+            optimizer._load_loss_scaler(state_dict["loss_scaler"])
         state_dict = optimizer.state_dict()
         optimizer.zero_grad(set_to_none=True)
     if len(state_dict["state"]) == 0:
-        return  # stateless optimizer (plain SGD without momentum)
+        # stateless optimizer (plain SGD without momentum), but for a scaler
+        if "loss_scaler" in state_dict:
+            optimizer._load_loss_scaler(broadcast_object(
+                state_dict["loss_scaler"], root_rank,
+                name="opt_state_loss_scaler", process_set=process_set))
+        return
 
     # ensure every rank has state initialized with the same structure: on
     # root, missing state stays; on workers we rebuild from root's metadata.
     meta = None
     if rank() == root_rank:
         meta = {
+            "loss_scaler": state_dict.get("loss_scaler"),
             "param_groups": state_dict["param_groups"],
             "state_keys": {
                 pid: [(k, (tuple(v.shape), str(v.dtype)) if torch.is_tensor(v)
@@ -179,3 +190,5 @@ def broadcast_optimizer_state(optimizer, root_rank, model=None,
             for k, v in meta_g.items():
                 if k != "params":
                     g[k] = v
+        if meta["loss_scaler"] is not None:
+            optimizer._load_loss_scaler(meta["loss_scaler"])
