@@ -231,6 +231,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grad_coef") = py::none(),
         py::arg("model_params") = py::none(), py::arg("skip") = py::none());
 
+  // -> the fp32 trust ratio of every parameter, in input order
+  m.def("fused_lars_step",
+        [opt_tensor, opt_list](std::vector<at::Tensor> params,
+                     std::vector<at::Tensor> grads,
+                     std::vector<at::Tensor> momenta, double lr,
+                     double momentum, double weight_decay,
+                     double trust_coefficient, double eps, bool nesterov,
+                     bool trust_clip, bool adapt, py::object grad_coef,
+                     OptTensors model_params, py::object skip) {
+          return hvd::gpu::FusedLarsStep(params, grads, momenta, lr, momentum,
+                                         weight_decay, trust_coefficient, eps,
+                                         nesterov, trust_clip, adapt,
+                                         opt_tensor(grad_coef),
+                                         opt_list(model_params),
+                                         opt_tensor(skip));
+        },
+        py::arg("params"), py::arg("grads"), py::arg("momenta"),
+        py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("trust_coefficient"), py::arg("eps"), py::arg("nesterov"),
+        py::arg("trust_clip"), py::arg("adapt"),
+        py::arg("grad_coef") = py::none(),
+        py::arg("model_params") = py::none(), py::arg("skip") = py::none());
+
   m.def("fused_bn_relu_forward",
         [](at::Tensor x, py::object residual, at::Tensor gamma, at::Tensor beta,
            at::Tensor rm, at::Tensor rv, double momentum, double eps) {

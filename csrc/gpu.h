@@ -116,7 +116,7 @@ at::Tensor MultiTensorScaledGradNorm(
 // tensors[i] *= coef in place; coef is a 1-element fp32 device tensor.
 void MultiTensorScale(std::vector<at::Tensor>& tensors, at::Tensor coef);
 
-// The three steps below take dense fp32 tensors of one GPU, lists of one
+// The steps below take dense fp32 tensors of one GPU, lists of one
 // length, a parameter's tensors of one size and layout; anything else throws
 // before the first launch.  An empty tensor is skipped.
 //
@@ -172,6 +172,29 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                          double beta1, double beta2, double eps,
                          double weight_decay, int64_t step,
                          bool bias_correction, bool adapt,
+                         at::Tensor grad_coef = at::Tensor(),
+                         const std::vector<at::Tensor>* model_params = nullptr,
+                         at::Tensor skip = at::Tensor());
+
+// Fused LARS step (lars_kernels.hip), under the rules of the three steps
+// above (`momenta` is always read and written).  With g' = g * grad_coef, per
+// tensor:
+//   trust = trust_coefficient * |p| / (|g'| + weight_decay * |p| + eps) when
+//           `adapt` and both norms are > 0, else 1; with trust_clip such a
+//           ratio becomes min(trust / lr, 1)
+//   d = trust * (g' + weight_decay * p),  m = momentum * m + d,
+//   p -= lr * (nesterov ? d + momentum * m : m)
+// Three launches per 48 tensors on torch's current stream, no host
+// synchronisation.  -> fp32 [params.size()], the trust ratio applied to each
+// parameter (1 for an empty one, and for every one when skip is set); bitwise
+// reproducible for identical inputs, and with model_params bitwise the
+// masters, momenta and ratios of the fp32 step on the widened gradients.
+at::Tensor FusedLarsStep(std::vector<at::Tensor>& params,
+                         std::vector<at::Tensor>& grads,
+                         std::vector<at::Tensor>& momenta, double lr,
+                         double momentum, double weight_decay,
+                         double trust_coefficient, double eps, bool nesterov,
+                         bool trust_clip, bool adapt,
                          at::Tensor grad_coef = at::Tensor(),
                          const std::vector<at::Tensor>* model_params = nullptr,
                          at::Tensor skip = at::Tensor());

@@ -86,14 +86,14 @@ hipError_t AdasumDotsLaunch(const AdasumBatchArgs& args, int dt, double* dots,
 hipError_t AdasumScaledAddLaunch(const AdasumBatchArgs& args, int dt,
                                  const double* dots, hipStream_t stream);
 
-// ---- Multi-tensor kernels: clip, fused SGD / AdamW / LAMB ------------------
+// ---- Multi-tensor kernels: clip, fused SGD / AdamW / LAMB / LARS -----------
 // All take one by-value descriptor batch of at most kCopyBatchCapacity dense
 // tensors, filled by multi_tensor.cc: ROWS rows of device pointers (tensor t
 // is ptr[row][t]) and the element counts.  SGD and AdamW give every
-// descriptor a fixed number of blocks.  The CHUNKED kernels (clip, LAMB) give
-// every block one kChunkElems-element chunk of one tensor: block_prefix[t] is
-// the first block of tensor t and block_prefix[count] the grid size, so work
-// is balanced by elements whatever the tensor sizes.
+// descriptor a fixed number of blocks.  The CHUNKED kernels (clip, LAMB, LARS)
+// give every block one kChunkElems-element chunk of one tensor:
+// block_prefix[t] is the first block of tensor t and block_prefix[count] the
+// grid size, so work is balanced by elements whatever the tensor sizes.
 constexpr long long kChunkElems = 8192;
 
 inline long long ChunkBlocks(long long numel) {
@@ -103,11 +103,12 @@ inline long long ChunkBlocks(long long numel) {
 struct ChunkFields {
   unsigned int block_prefix[kCopyBatchCapacity + 1] = {0};
   // first workspace slot of this launch: block b reduces into slot
-  // partial_base + b (a pair of floats for LAMB)
+  // partial_base + b (a pair of floats for LAMB and LARS)
   unsigned long long partial_base = 0;
 };
 struct IndexFields {
-  // slot of each tensor in a call-wide per-tensor output (LAMB's trust array)
+  // slot of each tensor in a call-wide per-tensor output (the trust array of
+  // LAMB and LARS)
   unsigned int out_index[kCopyBatchCapacity];
 };
 template <int> struct NoFields {};
@@ -128,11 +129,11 @@ struct MultiTensorArgs
 enum MultiTensorRow {
   kRowParam = 0,
   kRowGrad = 1,
-  kRowMomentum = 2,  // SGD; null when momentum == 0
+  kRowMomentum = 2,  // SGD (null when momentum == 0), LARS
   kRowExpAvg = 2,    // AdamW, LAMB
   kRowExpAvgSq = 3,
   // master-weight kernels: the fp16/bf16 model parameter, written only
-  kRowSgdModel = 3,
+  kRowSgdModel = 3,  // SGD, LARS
   kRowModel = 4,  // AdamW, LAMB
 };
 
@@ -155,6 +156,11 @@ static_assert(sizeof(SgdMasterBatchArgs) == 1928 &&
                   sizeof(LambMasterBatchArgs) == 2712,
               "kernarg bytes: one 384-byte pointer row more than the fp32 "
               "structs, under 4 KB");
+using LarsBatchArgs = MultiTensorArgs<3, true, true>;
+using LarsMasterBatchArgs = MultiTensorArgs<4, true, true>;
+static_assert(sizeof(LarsBatchArgs) == 1944 &&
+                  sizeof(LarsMasterBatchArgs) == 2328,
+              "kernarg bytes: LAMB's structs less one pointer row, under 4 KB");
 
 // ---- Fused SGD (sgd_kernels.hip) ------------------------------------------
 // grad_coef: null, or a device fp32 scalar every gradient element is
@@ -289,6 +295,57 @@ hipError_t LambTrustLaunch(const LambMasterBatchArgs& args,
                            hipStream_t stream);
 hipError_t LambUpdateMasterLaunch(const LambMasterBatchArgs& args, int dt,
                                   const LambScalars& s, const float* trust,
+                                  const float* skip, hipStream_t stream);
+
+// ---- Fused LARS (lars_kernels.hip) -----------------------------------------
+// Chunked.  Momentum SGD whose step is scaled per tensor by a trust ratio.
+// Three launches per batch:
+//   1. norms: g' = g * *grad_coef formed as read; block b writes sum(p^2) and
+//      sum(g'^2) of its chunk to partials[2 * (partial_base + b) + {0, 1}].
+//      Element e of a chunk always goes to lane (e / 4) % 256, accumulator
+//      e % 4, in rising order, whatever the alignment and the gradient dtype,
+//      so the sums of a master-weight launch are bitwise those of the fp32
+//      launch on the widened gradient
+//   2. trust: one block per tensor sums that tensor's slots in a fixed order
+//      in fp64 (no atomics: bitwise reproducible), wn = |p|, gn = |g'|, and
+//      writes trust[out_index[t]] =
+//        trust_coefficient * wn / (gn + weight_decay * wn + eps)
+//      if adapt and both norms are > 0 (false for NaN), else 1; with
+//      trust_clip a ratio r of the first kind becomes r / lr if that is < 1,
+//      else 1 (fp32, so lr == 0 gives 1)
+//   3. update: d = trust * (g' + weight_decay * p), m = momentum * m + d,
+//      p -= lr * (nesterov ? d + momentum * m : m)
+// With a set skip flag 1. and 3. touch nothing and 2. writes a ratio of 1 for
+// each of its tensors without reading the partials.
+struct LarsScalars {
+  float lr, momentum, weight_decay, trust_coefficient, eps;
+  bool nesterov, trust_clip, adapt;
+};
+
+// grad_coef as in FusedSgdLaunch: 1. and 3. both apply it as they read g.
+hipError_t LarsNormsLaunch(const LarsBatchArgs& args, const float* grad_coef,
+                           const float* skip, float* partials,
+                           hipStream_t stream);
+hipError_t LarsTrustLaunch(const LarsBatchArgs& args, const LarsScalars& s,
+                           const float* partials, const float* skip,
+                           float* trust, hipStream_t stream);
+hipError_t LarsUpdateLaunch(const LarsBatchArgs& args, const LarsScalars& s,
+                            const float* grad_coef, const float* trust,
+                            const float* skip, hipStream_t stream);
+// Master weights (dt in {DT_F16, DT_BF16}, one per launch): kRowParam holds
+// the fp32 master, whose norm 1. takes, kRowGrad a gradient of type dt; 3.
+// writes the master and, rounded to nearest-even, the model parameter of type
+// dt in kRowSgdModel.
+hipError_t LarsNormsMasterLaunch(const LarsMasterBatchArgs& args, int dt,
+                                 const float* grad_coef, const float* skip,
+                                 float* partials, hipStream_t stream);
+hipError_t LarsTrustLaunch(const LarsMasterBatchArgs& args,
+                           const LarsScalars& s, const float* partials,
+                           const float* skip, float* trust,
+                           hipStream_t stream);
+hipError_t LarsUpdateMasterLaunch(const LarsMasterBatchArgs& args, int dt,
+                                  const LarsScalars& s,
+                                  const float* grad_coef, const float* trust,
                                   const float* skip, hipStream_t stream);
 
 // ---- Fused BatchNorm(+Add)+ReLU (bn_kernels.hip) --------------------------

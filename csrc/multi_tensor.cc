@@ -1,6 +1,7 @@
 // Host side of the multi-tensor kernels: global-norm clipping
-// (clip_kernels.hip) and the fused SGD / AdamW / LAMB steps
-// (sgd_kernels.hip, adamw_kernels.hip, lamb_kernels.hip), declared in gpu.h.
+// (clip_kernels.hip) and the fused SGD / AdamW / LAMB / LARS steps
+// (sgd_kernels.hip, adamw_kernels.hip, lamb_kernels.hip, lars_kernels.hip),
+// declared in gpu.h.
 // Every entry point validates all of its tensors before the first launch (a
 // throw must not leave half of them updated), then fills descriptor batches
 // (MultiTensorArgs, kernels.h) through a Batcher, on torch's current stream.
@@ -426,6 +427,72 @@ at::Tensor FusedLambStep(std::vector<at::Tensor>& params,
                               skip_ptr, trust.data_ptr<float>(), stream));
     HIP_CHECK(LambUpdateLaunch(args, s, trust.data_ptr<float>(), skip_ptr,
                                stream));
+    base += args.block_prefix[args.count];
+  });
+  for (int64_t i = 0; i < n; ++i) batch.Add(rows, (size_t)i, (unsigned int)i);
+  batch.Flush();
+  return trust;
+}
+
+at::Tensor FusedLarsStep(std::vector<at::Tensor>& params,
+                         std::vector<at::Tensor>& grads,
+                         std::vector<at::Tensor>& momenta, double lr,
+                         double momentum, double weight_decay,
+                         double trust_coefficient, double eps, bool nesterov,
+                         bool trust_clip, bool adapt, at::Tensor grad_coef,
+                         const std::vector<at::Tensor>* model_params,
+                         at::Tensor skip) {
+  Rows rows{&params, &grads, &momenta};
+  const TupleInfo info = CheckTuples("fused_lars_step", "grads and momenta",
+                                     rows, true, model_params);
+  const int64_t n = (int64_t)params.size();
+  c10::hip::HIPGuard guard(info.device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(info.device).stream();
+  const float* coef = GradCoefPtr(grad_coef, info.device);
+  const float* skip_ptr = SkipPtr(skip, info.device);
+  auto f32 =
+      at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, info.device);
+  // sized for the whole call; every slot is written by exactly one block
+  // before the trust kernel of its batch reads it
+  at::Tensor partials =
+      at::empty({std::max<int64_t>(2 * info.chunk_blocks, 1)}, f32);
+  // empty tensors take no descriptor: their ratio is the preset 1
+  at::Tensor trust = info.any_empty ? at::ones({n}, f32) : at::empty({n}, f32);
+  LarsScalars s;
+  s.lr = (float)lr;
+  s.momentum = (float)momentum;
+  s.weight_decay = (float)weight_decay;
+  s.trust_coefficient = (float)trust_coefficient;
+  s.eps = (float)eps;
+  s.nesterov = nesterov;
+  s.trust_clip = trust_clip;
+  s.adapt = adapt;
+  unsigned long long base = 0;
+  if (model_params) {
+    rows.push_back(model_params);
+    ForEachMasterBatch<LarsMasterBatchArgs>(
+        rows, true, [&](LarsMasterBatchArgs& args, int dt) {
+          args.partial_base = base;
+          HIP_CHECK(LarsNormsMasterLaunch(args, dt, coef, skip_ptr,
+                                          partials.data_ptr<float>(), stream));
+          HIP_CHECK(LarsTrustLaunch(args, s, partials.data_ptr<float>(),
+                                    skip_ptr, trust.data_ptr<float>(),
+                                    stream));
+          HIP_CHECK(LarsUpdateMasterLaunch(args, dt, s, coef,
+                                           trust.data_ptr<float>(), skip_ptr,
+                                           stream));
+          base += args.block_prefix[args.count];
+        });
+    return trust;
+  }
+  Batcher<LarsBatchArgs> batch([&](LarsBatchArgs& args) {
+    args.partial_base = base;
+    HIP_CHECK(LarsNormsLaunch(args, coef, skip_ptr,
+                              partials.data_ptr<float>(), stream));
+    HIP_CHECK(LarsTrustLaunch(args, s, partials.data_ptr<float>(), skip_ptr,
+                              trust.data_ptr<float>(), stream));
+    HIP_CHECK(LarsUpdateLaunch(args, s, coef, trust.data_ptr<float>(),
+                               skip_ptr, stream));
     base += args.block_prefix[args.count];
   });
   for (int64_t i = 0; i < n; ++i) batch.Add(rows, (size_t)i, (unsigned int)i);

@@ -1,6 +1,6 @@
-// Device side shared by the multi-tensor kernels (clip, sgd, adamw and
-// lamb_kernels.hip): the chunked work division and fixed-order block sum of
-// clip and LAMB, and the per-element arithmetic of every optimizer kernel,
+// Device side shared by the multi-tensor kernels (clip, sgd, adamw, lamb and
+// lars_kernels.hip): the chunked work division and fixed-order block sum of
+// clip, LAMB and LARS, and the per-element arithmetic of every optimizer kernel,
 // stated once and called from the kernel's 16-byte loop and its tail loop.
 #pragma once
 
@@ -138,6 +138,20 @@ __device__ __forceinline__ void load_lp_vec(const T* base, long long i,
 #pragma unroll
   for (int k = 0; k < 8; ++k) x[k] = (float)in.e[k];
 }
+// 4 values of a 2-byte type in one 8-byte load (LARS' norm pass, which takes
+// 4 elements per lane whatever the gradient's type).
+template <typename T>
+__device__ __forceinline__ void load_lp_quad(const T* base, long long i,
+                                             float (&x)[4]) {
+  static_assert(sizeof(T) == 2, "fp16 or bf16");
+  union {
+    uint2 u;
+    T e[4];
+  } in;
+  in.u = ((const uint2*)base)[i];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = (float)in.e[k];
+}
 template <typename T>
 __device__ __forceinline__ void store_lp_vec(T* base, long long i,
                                              const float (&x)[8]) {
@@ -246,6 +260,31 @@ __device__ __forceinline__ void lamb_update_element(float& p, float m, float v,
                                                     float step,
                                                     const LambScalars& s) {
   p = fmaf(-step, lamb_u(p, m, v, s), p);
+}
+
+// LARS pass 1: p^2 and g'^2 into the caller's accumulators.
+template <bool HAS_COEF>
+__device__ __forceinline__ void lars_norms_element(float p, float g,
+                                                   float coef, float& pp,
+                                                   float& gg) {
+  if (HAS_COEF) g = scale_grad(g, coef);
+  pp = fmaf(p, p, pp);
+  gg = fmaf(g, g, gg);
+}
+
+// LARS pass 3: momentum SGD on d = trust * (g' + weight_decay * p).  d is
+// pinned, so a trust ratio of exactly 1 (a no-decay group) gives the bits of
+// sgd_element with dampening 0 on a buffer that starts at zero.
+template <bool NESTEROV, bool HAS_COEF>
+__device__ __forceinline__ void lars_element(float& p, float g, float& m,
+                                             float coef, float trust,
+                                             float lr, float momentum,
+                                             float weight_decay) {
+  if (HAS_COEF) g = scale_grad(g, coef);
+  const float d = pinned(trust * fmaf(weight_decay, p, g));
+  const float me = fmaf(momentum, m, d);  // m may be memory: one store
+  m = me;
+  p = fmaf(-lr, NESTEROV ? fmaf(momentum, me, d) : me, p);
 }
 
 }  // namespace gpu

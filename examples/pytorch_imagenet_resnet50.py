@@ -42,6 +42,10 @@ def parse_args():
                    help="fp16 wire compression for gradients")
     p.add_argument("--use-adasum", action="store_true")
     p.add_argument("--no-bf16", action="store_true")
+    p.add_argument("--lars", action="store_true",
+                   help="FusedLARS (layer-wise trust ratios) for large "
+                        "global batches, instead of momentum SGD")
+    p.add_argument("--lars-trust-coefficient", type=float, default=0.001)
     return p.parse_args()
 
 
@@ -62,10 +66,18 @@ def main():
     lr_scaler = hvd.size() if not args.use_adasum else 1
     if cuda and args.use_adasum:
         lr_scaler = hvd.local_size()
-    from horovod_amd.ops import FusedSGD
-    base_opt = (FusedSGD if cuda else torch.optim.SGD)(
-        model.parameters(), lr=args.base_lr * lr_scaler,
-        momentum=args.momentum, weight_decay=args.wd)
+    from horovod_amd.ops import FusedLARS, FusedSGD, split_decay_groups
+    if args.lars:
+        # trust ratios for the weights; biases and BatchNorm parameters go
+        # to a group without decay, which is plain momentum SGD
+        base_opt = FusedLARS(
+            split_decay_groups(model, args.wd), lr=args.base_lr * lr_scaler,
+            momentum=args.momentum,
+            trust_coefficient=args.lars_trust_coefficient)
+    else:
+        base_opt = (FusedSGD if cuda else torch.optim.SGD)(
+            model.parameters(), lr=args.base_lr * lr_scaler,
+            momentum=args.momentum, weight_decay=args.wd)
     compression = (hvd.Compression.fp16 if args.fp16_allreduce
                    else hvd.Compression.none)
     opt = hvd.DistributedOptimizer(

@@ -1,4 +1,4 @@
-"""Scaffold shared by FusedSGD, FusedAdamW and FusedLAMB.
+"""Scaffold shared by FusedSGD, FusedAdamW, FusedLAMB and FusedLARS.
 
 FusedOptimizer owns the max_grad_norm, master_weights and loss_scale options,
 `last_grad_norm`, the group defaults a foreign state dict may lack, and the
