@@ -268,6 +268,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return hvd::gpu::FusedBnReluBackward(x, y, dy, mean, invstd, gamma,
                                                need_res);
         });
+  m.def("fused_bn_pass",
+        [](int which, at::Tensor x, py::object a, py::object b, py::object out,
+           at::Tensor mean, at::Tensor invstd, at::Tensor gamma,
+           at::Tensor beta) {
+          auto opt = [](const py::object& o) {
+            return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
+          };
+          hvd::gpu::FusedBnPass(which, x, opt(a), opt(b), opt(out), mean,
+                                invstd, gamma, beta);
+        });
 
   // ---- SyncBatchNorm passes (None = absent optional tensor) ----------------
   m.def("sync_bn_stats",

@@ -1,7 +1,8 @@
 // Device-side pieces shared by the BatchNorm kernel TUs (bn_kernels.hip,
-// syncbn_kernels.hip): dtype conversion, 8-element vector access and the
-// fixed-channel grid sizing for channels_last activations with C % 8 == 0.
-// Included from .hip files only.
+// syncbn_kernels.hip): dtype conversion, 8-element vector access, and the
+// fixed-channel 8-wide ("cl-vec8") decomposition of channels_last
+// activations with C % 8 == 0: grid sizing, per-channel parameter loads and
+// the reduction tail.  Included from .hip files only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,9 @@
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
+#include <cstdint>
+
+#include "kernels.h"
 
 namespace hvd {
 namespace gpu {
@@ -73,6 +77,84 @@ inline int grid_for(long long total, int C, int vecs_per_thread = 1) {
   long long mult = vpr / g;  // blocks must be a multiple of this
   blocks = ((blocks + mult - 1) / mult) * mult;
   return (int)blocks;
+}
+
+// cl-vec8: the 8 per-channel values of a thread's octet as two 16-B loads
+// (the launcher checks that every parameter array is 16-B aligned); a null
+// array reads as `fill`.
+__device__ __forceinline__ void load_octet(float (&r)[8], const float* p,
+                                           int c0, float fill) {
+  if (p) {
+    const float4 lo = *(const float4*)(p + c0);
+    const float4 hi = *(const float4*)(p + c0 + 4);
+    r[0] = lo.x; r[1] = lo.y; r[2] = lo.z; r[3] = lo.w;
+    r[4] = hi.x; r[5] = hi.y; r[6] = hi.z; r[7] = hi.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = fill;
+  }
+}
+
+// first channel of the calling thread's octet; the grid has fewer than 2^31
+// threads and (threads * 8) % C == 0, so it is the same for every vector
+// the thread visits
+__device__ __forceinline__ int octet_channel(int C) {
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  return (int)(t % (unsigned)(C / 8)) * 8;
+}
+
+// cl-vec8 reduction tail: a thread's 2 x 8 partials of its channel octet ->
+// the block's LDS bins [2C] (zeroed, barrier passed) -> one atomicAdd per
+// (block, channel) into bank blockIdx % kBnBanks of [2C] floats.  When C/8
+// is a power of two below 64, lanes l and l ^ o of a wave hold the same
+// octet for every o that is a multiple of C/8: those fold by shuffle first,
+// so C/8 lanes per wave touch LDS instead of 64 colliding ones.
+__device__ __forceinline__ void octet_flush(float (&a)[8], float (&b)[8],
+                                            int c0, int C, float* lds,
+                                            float* __restrict__ banks) {
+  const int vpr = C / 8;
+  bool owner = true;
+  if (vpr < 64 && (vpr & (vpr - 1)) == 0) {
+    for (int o = 32; o >= vpr; o >>= 1) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        a[k] += __shfl_xor(a[k], o, 64);
+        b[k] += __shfl_xor(b[k], o, 64);
+      }
+    }
+    owner = (int)(threadIdx.x & 63) < vpr;
+  }
+  if (owner) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      atomicAdd(&lds[c0 + k], a[k]);
+      atomicAdd(&lds[C + c0 + k], b[k]);
+    }
+  }
+  __syncthreads();
+  float* bank = banks + (size_t)(blockIdx.x & (kBnBanks - 1)) * 2 * C;
+  for (int c = threadIdx.x; c < 2 * C; c += blockDim.x)
+    if (lds[c] != 0.f) atomicAdd(&bank[c], lds[c]);
+}
+
+// Grid of a cl-vec8 reduction.  Every block flushes 2C float atomics, and
+// measured on MI355X that flush, not the read, set the time of wide-C
+// shapes (64x512x28x28 bf16: 50 us at 1568 blocks against 14 us for the
+// planar kernel on the same bytes).  So on top of grid_for's 8 vectors per
+// thread the grid is capped at 2^18 flushed floats in all, but not below one
+// block per CU; the kernels keep several loads in flight per thread to make
+// up for the smaller grid.
+inline int vec8_reduce_grid(long long total, int C) {
+  const long long nvec = total / 8;
+  const long long max_blocks = std::max<long long>(256, (1LL << 17) / C);
+  long long vpt = (nvec + 256 * max_blocks - 1) / (256 * max_blocks);
+  return grid_for(total, C, (int)std::max<long long>(8, vpt));
+}
+
+inline bool aligned_to(const void* const* ptrs, int n, size_t a) {
+  for (int i = 0; i < n; ++i)
+    if (ptrs[i] && ((uintptr_t)ptrs[i] % a) != 0) return false;
+  return true;
 }
 
 }  // namespace

@@ -7,9 +7,13 @@
 // reductions into one) removes whole read/write passes.
 //
 // Layout contract: activations are channels_last-dense [count=N*H*W, C]
-// with C contiguous and C % 8 == 0 (every ResNet channel width).  Stats
-// accumulate in fp32 via per-block LDS bins (C <= 4096 -> <= 32 KB LDS)
-// flushed with one global atomicAdd per channel per block (guide G12).
+// with C contiguous and C % 8 == 0 (every ResNet channel width).  Every
+// kernel uses the fixed-channel 8-wide decomposition of bn_common.h: the
+// host sizes the grid so (threads * 8) % C == 0, so a thread meets the same
+// 8 channels at every grid stride and holds their parameters (two 16-B loads
+// per array) and partial sums in registers.  Stats accumulate in fp32 via
+// per-block LDS bins (C <= 4096 -> <= 32 KB LDS) flushed with one global
+// atomicAdd per channel per block into kBnBanks partial rows (guide G12).
 #include "bn_common.h"
 #include "kernels.h"
 
@@ -19,82 +23,53 @@ namespace gpu {
 namespace {
 
 // ---- forward stats: per-channel sum and sum-of-squares --------------------
-// Fixed-channel decomposition: the host sizes the grid so
-// (threads * 8) % C == 0, making every thread revisit the SAME 8 channels
-// each grid-stride iteration.  Partials live in registers; one LDS flush
-// per thread at block end, one global atomicAdd per (block, channel).
+// The read-only stream used to sit at 1.8 TB/s against 7.5 TB/s for the
+// apply pass.  Loads in flight were not the limit; the reduction tail was:
+//  - narrow C: with C/8 < 64 the lanes of a wave share C/8 octets, so the
+//    16 LDS atomicAdds per thread collided up to 64-way (8-way at C = 64);
+//    octet_flush folds same-octet lanes by shuffle first
+//  - wide C: every block flushes 2C global float atomics, which run at
+//    ~1.3 TB/s chip-wide, so 392 blocks at 64x2048x7x7 flushed 6.4 MB to
+//    read 12.8 MB; vec8_reduce_grid caps the flushed floats at 2^18
+// The smaller grid is made up for by 4 independent loads per thread.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_k(const T* __restrict__ x,
                                                   long long total, int C,
-                                                  float* __restrict__ sums,
-                                                  float* __restrict__ sqs) {
+                                                  float* __restrict__ banks) {
   extern __shared__ float lds[];  // [C] sum, [C] sq
-  float* lsum = lds;
-  float* lsq = lds + C;
   for (int c = threadIdx.x; c < 2 * C; c += blockDim.x) lds[c] = 0.f;
   __syncthreads();
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long nthreads = (long long)gridDim.x * blockDim.x;
   const long long nvec = total / 8;
-  const int c0 = (int)((tid * 8) % C);
+  const int c0 = octet_channel(C);
   float rsum[8] = {0}, rsq[8] = {0};
-  // 2x-unrolled independent loads.  NOTE: measured NO effect on the
-  // read-only stream's 1.8 TB/s ceiling (vs 7.5 TB/s for the read+write
-  // apply pass with the same loop structure) — the cap is not
-  // loads-in-flight; left in place since it costs nothing.  Open question
-  // recorded in NOTES.md.
-  long long i = tid;
-  for (; i + nthreads < nvec; i += 2 * nthreads) {
-    union { uint4 u; T e[8]; } v0, v1;
-    if (sizeof(T) == 2) {
-      v0.u = ((const uint4*)x)[i];
-      v1.u = ((const uint4*)x)[i + nthreads];
-    } else {
-      ((uint4*)&v0)[0] = ((const uint4*)x)[i * 2];
-      ((uint4*)&v0)[1] = ((const uint4*)x)[i * 2 + 1];
-      ((uint4*)&v1)[0] = ((const uint4*)x)[(i + nthreads) * 2];
-      ((uint4*)&v1)[1] = ((const uint4*)x)[(i + nthreads) * 2 + 1];
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float f0 = to_f<T>(v0.e[k]), f1 = to_f<T>(v1.e[k]);
-      rsum[k] += f0 + f1;
-      rsq[k] += f0 * f0 + f1 * f1;
-    }
-  }
-  for (; i < nvec; i += nthreads) {
-    union { uint4 u; T e[8]; } v;
-    if (sizeof(T) == 2) {
-      v.u = ((const uint4*)x)[i];
-    } else {
-      ((uint4*)&v)[0] = ((const uint4*)x)[i * 2];
-      ((uint4*)&v)[1] = ((const uint4*)x)[i * 2 + 1];
-    }
+  auto add = [&](const Vec8<T>& v) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float f = to_f<T>(v.e[k]);
       rsum[k] += f;
       rsq[k] += f * f;
     }
+  };
+  long long i = tid;
+  for (; i + 3 * nthreads < nvec; i += 4 * nthreads) {
+    Vec8<T> v0, v1, v2, v3;
+    load8(v0, x, i);
+    load8(v1, x, i + nthreads);
+    load8(v2, x, i + 2 * nthreads);
+    load8(v3, x, i + 3 * nthreads);
+    add(v0);
+    add(v1);
+    add(v2);
+    add(v3);
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    atomicAdd(&lsum[c0 + k], rsum[k]);
-    atomicAdd(&lsq[c0 + k], rsq[k]);
+  for (; i < nvec; i += nthreads) {
+    Vec8<T> v;
+    load8(v, x, i);
+    add(v);
   }
-  __syncthreads();
-  // banked flush: 2048 blocks all hitting the same C addresses serialize at
-  // the memory controller (measured 1.4 TB/s effective on the stats pass vs
-  // 7.3 TB/s for the atomic-free apply pass); spreading blocks over
-  // kBnBanks partial rows cuts per-address contention by the bank count
-  float* bsum = sums + (size_t)(blockIdx.x & (kBnBanks - 1)) * 2 * C;
-  float* bsq = bsum + C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    if (lsum[c] != 0.f || lsq[c] != 0.f) {
-      atomicAdd(&bsum[c], lsum[c]);
-      atomicAdd(&bsq[c], lsq[c]);
-    }
-  }
+  octet_flush(rsum, rsq, c0, C, lds, banks);
 }
 
 // ---- forward apply: y = relu(gamma*xhat + beta [+ residual]) --------------
@@ -107,42 +82,23 @@ __global__ __launch_bounds__(256) void bn_apply_relu_k(
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long nthreads = (long long)gridDim.x * blockDim.x;
   const long long nvec = total / 8;
-  // fixed-channel decomposition (see bn_stats_k): per-thread channel params
-  // load once into registers
-  const int c0 = (int)((tid * 8) % C);
+  const int c0 = octet_channel(C);
   float rm[8], ri[8], rg[8], rb[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    rm[k] = mean[c0 + k];
-    ri[k] = invstd[c0 + k];
-    rg[k] = gamma[c0 + k];
-    rb[k] = beta[c0 + k];
-  }
+  load_octet(rm, mean, c0, 0.f);
+  load_octet(ri, invstd, c0, 0.f);
+  load_octet(rg, gamma, c0, 1.f);
+  load_octet(rb, beta, c0, 0.f);
   for (long long i = tid; i < nvec; i += nthreads) {
-    union { uint4 u; T e[8]; } vx, vr, vy;
-    if (sizeof(T) == 2) {
-      vx.u = ((const uint4*)x)[i];
-      if (ADD) vr.u = ((const uint4*)res)[i];
-    } else {
-      ((uint4*)&vx)[0] = ((const uint4*)x)[i * 2];
-      ((uint4*)&vx)[1] = ((const uint4*)x)[i * 2 + 1];
-      if (ADD) {
-        ((uint4*)&vr)[0] = ((const uint4*)res)[i * 2];
-        ((uint4*)&vr)[1] = ((const uint4*)res)[i * 2 + 1];
-      }
-    }
+    Vec8<T> vx, vr, vy;
+    load8(vx, x, i);
+    if (ADD) load8(vr, res, i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float f = (to_f<T>(vx.e[k]) - rm[k]) * ri[k] * rg[k] + rb[k];
       if (ADD) f += to_f<T>(vr.e[k]);
       vy.e[k] = from_f<T>(f > 0.f ? f : 0.f);
     }
-    if (sizeof(T) == 2) {
-      ((uint4*)y)[i] = vy.u;
-    } else {
-      ((uint4*)y)[i * 2] = ((uint4*)&vy)[0];
-      ((uint4*)y)[i * 2 + 1] = ((uint4*)&vy)[1];
-    }
+    store8(y, i, vy);
   }
 }
 
@@ -153,70 +109,43 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_k(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
     T* __restrict__ g_out, const float* __restrict__ mean,
     const float* __restrict__ invstd, long long total, int C,
-    float* __restrict__ sum_g, float* __restrict__ sum_gx) {
-  extern __shared__ float lds[];
-  float* lg = lds;
-  float* lgx = lds + C;
+    float* __restrict__ banks) {
+  extern __shared__ float lds[];  // [C] sum(g), [C] sum(g * xhat)
   for (int c = threadIdx.x; c < 2 * C; c += blockDim.x) lds[c] = 0.f;
   __syncthreads();
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long nthreads = (long long)gridDim.x * blockDim.x;
   const long long nvec = total / 8;
-  const int c0 = (int)((tid * 8) % C);
-  float rmean[8], rinv[8], racc_g[8] = {0}, racc_gx[8] = {0};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    rmean[k] = mean[c0 + k];
-    rinv[k] = invstd[c0 + k];
-  }
+  const int c0 = octet_channel(C);
+  // sum(g * xhat) = invstd * sum(g * (x - mean)): invstd is applied once
+  // after the loop, which keeps 8 registers out of it
+  float rmean[8], racc_g[8] = {0}, racc_gx[8] = {0};
+  load_octet(rmean, mean, c0, 0.f);
+  // One vector of each of the three tensors in flight per thread.  Two of
+  // each took 102-128 VGPRs (4 waves/SIMD against 6-7 here), and holding
+  // that form to 7 waves spilled 156-188 B/lane to scratch.
   for (long long i = tid; i < nvec; i += nthreads) {
-    union { uint4 u; T e[8]; } vx, vy, vd, vg;
-    if (sizeof(T) == 2) {
-      vx.u = ((const uint4*)x)[i];
-      vy.u = ((const uint4*)y)[i];
-      vd.u = ((const uint4*)dy)[i];
-    } else {
-      ((uint4*)&vx)[0] = ((const uint4*)x)[i * 2];
-      ((uint4*)&vx)[1] = ((const uint4*)x)[i * 2 + 1];
-      ((uint4*)&vy)[0] = ((const uint4*)y)[i * 2];
-      ((uint4*)&vy)[1] = ((const uint4*)y)[i * 2 + 1];
-      ((uint4*)&vd)[0] = ((const uint4*)dy)[i * 2];
-      ((uint4*)&vd)[1] = ((const uint4*)dy)[i * 2 + 1];
-    }
+    Vec8<T> vx, vy, vd, vg;
+    load8(vx, x, i);
+    load8(vy, y, i);
+    load8(vd, dy, i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float gv = to_f<T>(vy.e[k]) > 0.f ? to_f<T>(vd.e[k]) : 0.f;
-      float xh = (to_f<T>(vx.e[k]) - rmean[k]) * rinv[k];
       racc_g[k] += gv;
-      racc_gx[k] += gv * xh;
+      racc_gx[k] += gv * (to_f<T>(vx.e[k]) - rmean[k]);
       if (WRITE_G) vg.e[k] = from_f<T>(gv);
     }
-    if (WRITE_G) {
-      if (sizeof(T) == 2) {
-        ((uint4*)g_out)[i] = vg.u;
-      } else {
-        ((uint4*)g_out)[i * 2] = ((uint4*)&vg)[0];
-        ((uint4*)g_out)[i * 2 + 1] = ((uint4*)&vg)[1];
-      }
-    }
+    if (WRITE_G) store8(g_out, i, vg);
   }
+  float rinv[8];
+  load_octet(rinv, invstd, c0, 0.f);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    atomicAdd(&lg[c0 + k], racc_g[k]);
-    atomicAdd(&lgx[c0 + k], racc_gx[k]);
-  }
-  __syncthreads();
-  float* bg = sum_g + (size_t)(blockIdx.x & (kBnBanks - 1)) * 2 * C;
-  float* bgx = bg + C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    if (lg[c] != 0.f || lgx[c] != 0.f) {
-      atomicAdd(&bg[c], lg[c]);
-      atomicAdd(&bgx[c], lgx[c]);
-    }
-  }
+  for (int k = 0; k < 8; ++k) racc_gx[k] *= rinv[k];
+  octet_flush(racc_g, racc_gx, c0, C, lds, banks);
 }
 
-// reduce the kBnBanks x [2C] partials into banks[0] (both fwd + bwd tails)
+// reduce the kBnBanks x [2C] partials into banks[0] (the backward tail)
 __global__ __launch_bounds__(256) void bn_bank_reduce_k(float* banks,
                                                         int C) {
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < 2 * C;
@@ -228,7 +157,9 @@ __global__ __launch_bounds__(256) void bn_bank_reduce_k(float* banks,
 }
 
 // ---- backward apply: dx = gamma*invstd*(g - sum_g/n - xhat*sum_gx/n) ------
-template <typename T>
+// FROM_G: `dy` is the g = dy*(y>0) that bn_bwd_stats_k<WRITE_G> stored
+// (exact: each element is dy itself or 0), so y is not read at all.
+template <typename T, bool FROM_G>
 __global__ __launch_bounds__(256) void bn_bwd_apply_k(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
     T* __restrict__ dx, const float* __restrict__ mean,
@@ -238,44 +169,68 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long nthreads = (long long)gridDim.x * blockDim.x;
   const long long nvec = total / 8;
-  const int c0 = (int)((tid * 8) % C);
+  const int c0 = octet_channel(C);
   float rmean[8], rinv[8], rgi[8], rsg[8], rsgx[8];
+  load_octet(rmean, mean, c0, 0.f);
+  load_octet(rinv, invstd, c0, 0.f);
+  load_octet(rgi, gamma, c0, 1.f);
+  load_octet(rsg, sum_g, c0, 0.f);
+  load_octet(rsgx, sum_gx, c0, 0.f);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    rmean[k] = mean[c0 + k];
-    rinv[k] = invstd[c0 + k];
-    rgi[k] = gamma[c0 + k] * rinv[k];
-    rsg[k] = sum_g[c0 + k] * inv_count;
-    rsgx[k] = sum_gx[c0 + k] * inv_count;
+    rgi[k] = rgi[k] * rinv[k];
+    rsg[k] = rsg[k] * inv_count;
+    rsgx[k] = rsgx[k] * inv_count;
   }
   for (long long i = tid; i < nvec; i += nthreads) {
-    union { uint4 u; T e[8]; } vx, vy, vd, vo;
-    if (sizeof(T) == 2) {
-      vx.u = ((const uint4*)x)[i];
-      vy.u = ((const uint4*)y)[i];
-      vd.u = ((const uint4*)dy)[i];
-    } else {
-      ((uint4*)&vx)[0] = ((const uint4*)x)[i * 2];
-      ((uint4*)&vx)[1] = ((const uint4*)x)[i * 2 + 1];
-      ((uint4*)&vy)[0] = ((const uint4*)y)[i * 2];
-      ((uint4*)&vy)[1] = ((const uint4*)y)[i * 2 + 1];
-      ((uint4*)&vd)[0] = ((const uint4*)dy)[i * 2];
-      ((uint4*)&vd)[1] = ((const uint4*)dy)[i * 2 + 1];
-    }
+    Vec8<T> vx, vy, vd, vo;
+    load8(vx, x, i);
+    if (!FROM_G) load8(vy, y, i);
+    load8(vd, dy, i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float gv = to_f<T>(vy.e[k]) > 0.f ? to_f<T>(vd.e[k]) : 0.f;
+      float gv = FROM_G ? to_f<T>(vd.e[k])
+                        : (to_f<T>(vy.e[k]) > 0.f ? to_f<T>(vd.e[k]) : 0.f);
       float xh = (to_f<T>(vx.e[k]) - rmean[k]) * rinv[k];
       float v = rgi[k] * (gv - rsg[k] - xh * rsgx[k]);
       vo.e[k] = from_f<T>(v);
     }
-    if (sizeof(T) == 2) {
-      ((uint4*)dx)[i] = vo.u;
-    } else {
-      ((uint4*)dx)[i * 2] = ((uint4*)&vo)[0];
-      ((uint4*)dx)[i * 2 + 1] = ((uint4*)&vo)[1];
-    }
+    store8(dx, i, vo);
   }
+}
+
+// ---- forward epilogue: fold the banks, mean/invstd, running stats ---------
+// One thread per channel over (C + 255) / 256 blocks; the 2 x kBnBanks loads
+// of a thread are independent and coalesced across the block.
+__global__ __launch_bounds__(256) void bn_finalize_k(
+    const float* __restrict__ banks, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, long long count, float momentum,
+    float eps, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float inv_n = 1.0f / (float)count;
+  const float ub = count > 1 ? (float)count / (float)(count - 1) : 1.0f;
+  float s = 0.f, q = 0.f;
+#pragma unroll 16
+  for (int b = 0; b < kBnBanks; ++b) {
+    s += banks[(size_t)b * 2 * C + c];
+    q += banks[(size_t)b * 2 * C + C + c];
+  }
+  float m = s * inv_n;
+  float v = q * inv_n - m * m;
+  mean[c] = m;
+  invstd[c] = rsqrtf(v + eps);
+  if (running_mean) {
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * v * ub;
+  }
+}
+
+// the cl-vec8 kernels read activations and per-channel arrays as 16-B vectors
+template <size_t N>
+bool aligned16(const void* const (&ptrs)[N]) {
+  return aligned_to(ptrs, (int)N, 16);
 }
 
 }  // namespace
@@ -288,34 +243,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(
     default: return hipErrorInvalidValue;                         \
   }
 
-__global__ __launch_bounds__(256) void bn_finalize_k(
-    const float* __restrict__ banks, float* __restrict__ mean,
-    float* __restrict__ invstd, float* __restrict__ running_mean,
-    float* __restrict__ running_var, long long count, float momentum,
-    float eps, int C) {
-  const float inv_n = 1.0f / (float)count;
-  const float ub = count > 1 ? (float)count / (float)(count - 1) : 1.0f;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    // banks were reduced into row 0 by bn_bank_reduce_k (multi-block; a
-    // single-block 64x2C read here cost ~40 us at C=2048)
-    float m = banks[c] * inv_n;
-    float v = banks[C + c] * inv_n - m * m;
-    mean[c] = m;
-    invstd[c] = rsqrtf(v + eps);
-    if (running_mean) {
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-      running_var[c] =
-          (1.f - momentum) * running_var[c] + momentum * v * ub;
-    }
-  }
-}
-
 hipError_t BnFinalizeLaunch(const float* banks, float* mean, float* invstd,
                             float* running_mean, float* running_var,
                             long long count, float momentum, float eps,
                             int C, hipStream_t stream) {
-  bn_finalize_k<<<1, 256, 0, stream>>>(banks, mean, invstd, running_mean,
-                                       running_var, count, momentum, eps, C);
+  bn_finalize_k<<<(C + 255) / 256, 256, 0, stream>>>(
+      banks, mean, invstd, running_mean, running_var, count, momentum, eps, C);
   return hipGetLastError();
 }
 
@@ -326,11 +259,13 @@ hipError_t BnBankReduceLaunch(float* banks, int C, hipStream_t stream) {
 }
 
 hipError_t BnStatsLaunch(const void* x, long long total, int C, int dt,
-                         float* sums, float* sqs, hipStream_t stream) {
-  int blocks = grid_for(total, C, 8);
+                         float* banks, hipStream_t stream) {
+  const void* const ptrs[] = {x};
+  if (!aligned16(ptrs)) return hipErrorInvalidValue;
+  int blocks = vec8_reduce_grid(total, C);
   size_t lds = 2 * (size_t)C * sizeof(float);
   DISPATCH_T(dt, (bn_stats_k<scalar_t><<<blocks, 256, lds, stream>>>(
-                     (const scalar_t*)x, total, C, sums, sqs)));
+                     (const scalar_t*)x, total, C, banks)));
   return hipGetLastError();
 }
 
@@ -339,6 +274,8 @@ hipError_t BnApplyReluLaunch(const void* x, const void* res, void* y,
                              const float* gamma, const float* beta,
                              long long total, int C, int dt,
                              hipStream_t stream) {
+  const void* const ptrs[] = {x, res, y, mean, invstd, gamma, beta};
+  if (!aligned16(ptrs)) return hipErrorInvalidValue;
   int blocks = grid_for(total, C);
   if (res) {
     DISPATCH_T(dt, (bn_apply_relu_k<scalar_t, true><<<blocks, 256, 0, stream>>>(
@@ -356,20 +293,21 @@ hipError_t BnApplyReluLaunch(const void* x, const void* res, void* y,
 hipError_t BnBwdStatsLaunch(const void* x, const void* y, const void* dy,
                             void* g_out, const float* mean,
                             const float* invstd, long long total, int C,
-                            int dt, float* sum_g, float* sum_gx,
-                            hipStream_t stream) {
-  int blocks = grid_for(total, C, 8);
+                            int dt, float* banks, hipStream_t stream) {
+  const void* const ptrs[] = {x, y, dy, g_out, mean, invstd};
+  if (!aligned16(ptrs)) return hipErrorInvalidValue;
+  int blocks = vec8_reduce_grid(total, C);
   size_t lds = 2 * (size_t)C * sizeof(float);
   if (g_out) {
     DISPATCH_T(dt,
                (bn_bwd_stats_k<scalar_t, true><<<blocks, 256, lds, stream>>>(
                    (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
-                   (scalar_t*)g_out, mean, invstd, total, C, sum_g, sum_gx)));
+                   (scalar_t*)g_out, mean, invstd, total, C, banks)));
   } else {
     DISPATCH_T(dt,
                (bn_bwd_stats_k<scalar_t, false><<<blocks, 256, lds, stream>>>(
                    (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
-                   nullptr, mean, invstd, total, C, sum_g, sum_gx)));
+                   nullptr, mean, invstd, total, C, banks)));
   }
   return hipGetLastError();
 }
@@ -379,11 +317,21 @@ hipError_t BnBwdApplyLaunch(const void* x, const void* y, const void* dy,
                             const float* gamma, const float* sum_g,
                             const float* sum_gx, long long total, int C,
                             int dt, float inv_count, hipStream_t stream) {
+  const void* const ptrs[] = {x,      y,     dy,    dx,    mean,
+                              invstd, gamma, sum_g, sum_gx};
+  if (!aligned16(ptrs)) return hipErrorInvalidValue;
   int blocks = grid_for(total, C);
-  DISPATCH_T(dt, (bn_bwd_apply_k<scalar_t><<<blocks, 256, 0, stream>>>(
-                     (const scalar_t*)x, (const scalar_t*)y,
-                     (const scalar_t*)dy, (scalar_t*)dx, mean, invstd, gamma,
-                     sum_g, sum_gx, total, C, inv_count)));
+  if (y) {
+    DISPATCH_T(dt, (bn_bwd_apply_k<scalar_t, false><<<blocks, 256, 0, stream>>>(
+                       (const scalar_t*)x, (const scalar_t*)y,
+                       (const scalar_t*)dy, (scalar_t*)dx, mean, invstd, gamma,
+                       sum_g, sum_gx, total, C, inv_count)));
+  } else {
+    DISPATCH_T(dt, (bn_bwd_apply_k<scalar_t, true><<<blocks, 256, 0, stream>>>(
+                       (const scalar_t*)x, nullptr, (const scalar_t*)dy,
+                       (scalar_t*)dx, mean, invstd, gamma, sum_g, sum_gx,
+                       total, C, inv_count)));
+  }
   return hipGetLastError();
 }
 

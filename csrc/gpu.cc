@@ -1531,6 +1531,20 @@ void AdasumCombine(std::vector<at::Tensor>& a, std::vector<at::Tensor>& b) {
 }
 
 // ---- Fused BN(+Add)+ReLU host side ----------------------------------------
+namespace {
+
+// The kernels read per-channel arrays as 16-B vectors of fp32.  A parameter
+// of another dtype, a strided one, or one that is a view at an odd offset
+// into a flat buffer goes through an aligned fp32 copy.
+at::Tensor BnParamF32(const at::Tensor& t) {
+  if (t.scalar_type() == at::kFloat && t.is_contiguous() &&
+      (uintptr_t)t.data_ptr() % 16 == 0)
+    return t;
+  return t.to(at::kFloat).clone(at::MemoryFormat::Contiguous);
+}
+
+}  // namespace
+
 // Returns {y, save_mean, save_invstd}.  Small per-channel math ([C] tensors)
 // runs through ATen; the big passes are the CDNA4 kernels.
 std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
@@ -1543,6 +1557,13 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
               "fused BN requires channels_last layout");
   int64_t C = x.size(1);
   TORCH_CHECK(C % 8 == 0 && C <= 4096, "fused BN requires C % 8 == 0, C <= 4096");
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C,
+              "fused BN: weight and bias must have C elements");
+  TORCH_CHECK(!residual.defined() ||
+                  (residual.sizes() == x.sizes() &&
+                   residual.scalar_type() == x.scalar_type() &&
+                   residual.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              "fused BN: residual must match x in shape, dtype and layout");
   int device = (int)x.get_device();
   c10::hip::HIPGuard guard(device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
@@ -1555,6 +1576,7 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
   // (mean/invstd + running-stat update) runs in bn_finalize_k — the
   // previous ~10 tiny ATen launches per BN layer cost 3.5 ms/step of pure
   // launch overhead at batch 64 (53 layers, fwd+bwd)
+  // mean / invstd sit behind the banks, 16-B aligned because C % 8 == 0
   const int64_t bank_elems = (int64_t)kBnBanks * 2 * C;
   at::Tensor ws = at::empty({bank_elems + 2 * C}, fopts);
   float* wsp = ws.data_ptr<float>();
@@ -1562,9 +1584,12 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
   float* invstd_p = mean_p + C;
   HIP_CHECK(hipMemsetAsync(wsp, 0, (size_t)bank_elems * sizeof(float),
                            stream));
-  HIP_CHECK(BnStatsLaunch(x.data_ptr(), total, (int)C, dt, wsp, nullptr,
-                          stream));
-  HIP_CHECK(BnBankReduceLaunch(wsp, (int)C, stream));
+  HIP_CHECK(BnStatsLaunch(x.data_ptr(), total, (int)C, dt, wsp, stream));
+  // running stats may sit at any offset: bn_finalize_k reads them per channel
+  TORCH_CHECK(!running_mean.defined() ||
+                  (running_var.defined() && running_mean.numel() == C &&
+                   running_var.numel() == C),
+              "fused BN: running stats must have C elements");
   bool stats_f32 = running_mean.defined() &&
                    running_mean.scalar_type() == at::kFloat &&
                    running_mean.is_contiguous() &&
@@ -1586,14 +1611,8 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
     running_var.mul_(1 - momentum)
         .add_((var * ub).to(running_var.scalar_type()), momentum);
   }
-  at::Tensor gamma_f =
-      gamma.scalar_type() == at::kFloat && gamma.is_contiguous()
-          ? gamma
-          : gamma.to(at::kFloat).contiguous();
-  at::Tensor beta_f =
-      beta.scalar_type() == at::kFloat && beta.is_contiguous()
-          ? beta
-          : beta.to(at::kFloat).contiguous();
+  at::Tensor gamma_f = BnParamF32(gamma);
+  at::Tensor beta_f = BnParamF32(beta);
   at::Tensor y = at::empty_like(x);
   HIP_CHECK(BnApplyReluLaunch(
       x.data_ptr(), residual.defined() ? residual.data_ptr() : nullptr,
@@ -1616,6 +1635,17 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
   int dt = (int)DataTypeFromTorch(x.scalar_type());
   if (!dy.is_contiguous(at::MemoryFormat::ChannelsLast))
     dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(x.dim() == 4 && C % 8 == 0 && C <= 4096 &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  y.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "fused BN backward: x and y must be channels_last with "
+              "C % 8 == 0, C <= 4096");
+  TORCH_CHECK(y.sizes() == x.sizes() && dy.sizes() == x.sizes() &&
+                  y.scalar_type() == x.scalar_type() &&
+                  dy.scalar_type() == x.scalar_type() &&
+                  mean.numel() == C && invstd.numel() == C &&
+                  gamma.numel() == C,
+              "fused BN backward: mismatched shapes or dtypes");
 
   auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
   at::Tensor sums = at::empty({(int64_t)kBnBanks * 2 * C}, fopts);
@@ -1624,21 +1654,24 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
                            (size_t)kBnBanks * 2 * C * sizeof(float), stream));
   at::Tensor dres;
   if (need_residual_grad) dres = at::empty_like(x);
+  // the forward's own mean / invstd are aligned views of its workspace
+  at::Tensor mean_f = BnParamF32(mean), invstd_f = BnParamF32(invstd);
   HIP_CHECK(BnBwdStatsLaunch(x.data_ptr(), y.data_ptr(), dy.data_ptr(),
                              need_residual_grad ? dres.data_ptr() : nullptr,
-                             mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                             total, (int)C, dt, bankp, nullptr, stream));
+                             mean_f.data_ptr<float>(),
+                             invstd_f.data_ptr<float>(), total, (int)C, dt,
+                             bankp, stream));
   HIP_CHECK(BnBankReduceLaunch(bankp, (int)C, stream));
-  at::Tensor gamma_f =
-      gamma.scalar_type() == at::kFloat && gamma.is_contiguous()
-          ? gamma
-          : gamma.to(at::kFloat).contiguous();
+  at::Tensor gamma_f = BnParamF32(gamma);
   at::Tensor dx = at::empty_like(x);
-  HIP_CHECK(BnBwdApplyLaunch(x.data_ptr(), y.data_ptr(), dy.data_ptr(),
-                             dx.data_ptr(), mean.data_ptr<float>(),
-                             invstd.data_ptr<float>(), gamma_f.data_ptr<float>(),
-                             bankp, bankp + C, total, (int)C, dt,
-                             (float)(1.0 / count), stream));
+  // Add variant: dres already holds g = dy * (y > 0) exactly, so the apply
+  // pass reads it and x instead of x, y and dy
+  HIP_CHECK(BnBwdApplyLaunch(
+      x.data_ptr(), need_residual_grad ? nullptr : y.data_ptr(),
+      need_residual_grad ? dres.data_ptr() : dy.data_ptr(), dx.data_ptr(),
+      mean_f.data_ptr<float>(), invstd_f.data_ptr<float>(),
+      gamma_f.data_ptr<float>(), bankp, bankp + C, total, (int)C, dt,
+      (float)(1.0 / count), stream));
   at::Tensor sum_g = sums.narrow(0, 0, C), sum_gx = sums.narrow(0, C, C);
   at::Tensor dbeta = gamma.scalar_type() == at::kFloat
                          ? sum_g
@@ -1649,6 +1682,80 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
   std::vector<at::Tensor> out{dx, dgamma, dbeta};
   if (need_residual_grad) out.push_back(dres);
   return out;
+}
+
+// DIAGNOSTIC, not used by any module: one big pass of the fused path on its
+// own, as a layer issues it (the reductions with their memset), so that
+// examples/bn_pass_probe.py can time the passes from Python with the tensors
+// torch allocates (docs/benchmarks.md, per-pass table).  Pass 3 computes
+// nothing meaningful: see the stand-ins below.
+//   0 stats(x)                      1 apply(x, res = a or none) -> out
+//   2 bwd stats(x, y = a, dy = b) [-> g = out]
+//   3 bwd apply(x, y = a or none, dy or g = b) -> out
+void FusedBnPass(int which, at::Tensor x, at::Tensor a, at::Tensor b,
+                 at::Tensor out, at::Tensor mean, at::Tensor invstd,
+                 at::Tensor gamma, at::Tensor beta) {
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "fused BN requires channels_last layout");
+  int64_t C = x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C <= 4096, "fused BN requires C % 8 == 0, C <= 4096");
+  for (const at::Tensor* t : {&a, &b, &out})
+    TORCH_CHECK(!t->defined() ||
+                    (t->sizes() == x.sizes() &&
+                     t->scalar_type() == x.scalar_type() &&
+                     t->is_contiguous(at::MemoryFormat::ChannelsLast)),
+                "fused BN pass: activations must match x");
+  for (const at::Tensor* t : {&mean, &invstd, &gamma, &beta})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                    t->numel() == C,
+                "fused BN pass: per-channel arrays must be fp32 [C]");
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  int64_t total = x.numel();
+  int dt = (int)DataTypeFromTorch(x.scalar_type());
+  auto ptr = [](const at::Tensor& t) -> void* {
+    return t.defined() ? t.data_ptr() : nullptr;
+  };
+  const size_t bank_bytes = (size_t)kBnBanks * 2 * C * sizeof(float);
+  at::Tensor banks = at::empty(
+      {(int64_t)kBnBanks * 2 * C},
+      at::TensorOptions().dtype(at::kFloat).device(x.device()));
+  float* bankp = banks.data_ptr<float>();
+  const float* mp = mean.data_ptr<float>();
+  const float* ip = invstd.data_ptr<float>();
+  switch (which) {
+    case 0:
+      HIP_CHECK(hipMemsetAsync(bankp, 0, bank_bytes, stream));
+      HIP_CHECK(BnStatsLaunch(x.data_ptr(), total, (int)C, dt, bankp, stream));
+      break;
+    case 1:
+      TORCH_CHECK(out.defined(), "fused BN pass 1 needs out");
+      HIP_CHECK(BnApplyReluLaunch(x.data_ptr(), ptr(a), out.data_ptr(), mp, ip,
+                                  gamma.data_ptr<float>(),
+                                  beta.data_ptr<float>(), total, (int)C, dt,
+                                  stream));
+      break;
+    case 2:
+      TORCH_CHECK(a.defined() && b.defined(), "fused BN pass 2 needs y, dy");
+      HIP_CHECK(hipMemsetAsync(bankp, 0, bank_bytes, stream));
+      HIP_CHECK(BnBwdStatsLaunch(x.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                 ptr(out), mp, ip, total, (int)C, dt, bankp,
+                                 stream));
+      break;
+    case 3:
+      TORCH_CHECK(b.defined() && out.defined(),
+                  "fused BN pass 3 needs dy and out");
+      // the sums' values do not matter to the timing; mean stands in
+      HIP_CHECK(BnBwdApplyLaunch(x.data_ptr(), ptr(a), b.data_ptr(),
+                                 out.data_ptr(), mp, ip,
+                                 gamma.data_ptr<float>(), mp, ip, total,
+                                 (int)C, dt, 1.0f / (float)(total / C),
+                                 stream));
+      break;
+    default:
+      TORCH_CHECK(false, "fused BN pass: which must be 0..3");
+  }
 }
 
 // ---- SyncBatchNorm host side -----------------------------------------------

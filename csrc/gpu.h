@@ -66,6 +66,12 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
                                             at::Tensor dy, at::Tensor mean,
                                             at::Tensor invstd, at::Tensor gamma,
                                             bool need_residual_grad);
+// One big pass of the fused path on its own (per-pass timing probe):
+// which = 0 stats, 1 apply, 2 backward stats, 3 backward apply; a / b / out
+// may be undefined where the pass has no such tensor (see gpu.cc).
+void FusedBnPass(int which, at::Tensor x, at::Tensor a, at::Tensor b,
+                 at::Tensor out, at::Tensor mean, at::Tensor invstd,
+                 at::Tensor gamma, at::Tensor beta);
 
 // SyncBatchNorm passes around the two stats allreduces (syncbn_kernels.hip);
 // x is fp32/fp16/bf16, contiguous or channels_last (4-D/5-D).  weight, bias

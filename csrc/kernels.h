@@ -357,12 +357,18 @@ hipError_t LarsUpdateMasterLaunch(const LarsMasterBatchArgs& args, int dt,
 // memory controller under thousands of blocks.
 constexpr int kBnBanks = 64;
 
-// sums: banked partial buffer of kBnBanks * 2 * C floats (zeroed).
+// Every activation pointer and per-channel fp32 array below is read as 16-B
+// vectors; a launcher returns hipErrorInvalidValue for one that is not 16-B
+// aligned (running_mean / running_var are exempt: bn_finalize_k reads them
+// one channel per thread).
+//
+// banks: partial buffer of kBnBanks * 2 * C floats (zeroed): row b holds
+// [sum(C), sum of squares(C)] of the blocks with blockIdx % kBnBanks == b.
 hipError_t BnStatsLaunch(const void* x, long long total, int C, int dt,
-                         float* sums, float* sqs_unused, hipStream_t stream);
-// Per-channel epilogue in ONE kernel: bank-reduce + mean/invstd + running
-// stats — replaces ~10 tiny ATen launches per BN layer (measured 3.5
-// ms/step of pure launch overhead at batch 64).
+                         float* banks, hipStream_t stream);
+// Per-channel forward epilogue in ONE multi-block kernel: fold the banks +
+// mean/invstd + running stats.  Replaces ~10 tiny ATen launches per BN layer
+// (measured 3.5 ms/step of pure launch overhead at batch 64).
 hipError_t BnFinalizeLaunch(const float* banks, float* mean, float* invstd,
                             float* running_mean, float* running_var,
                             long long count, float momentum, float eps,
@@ -374,11 +380,14 @@ hipError_t BnApplyReluLaunch(const void* x, const void* res, void* y,
                              const float* gamma, const float* beta,
                              long long total, int C, int dt,
                              hipStream_t stream);
+// banks as in BnStatsLaunch, rows of [sum(g)(C), sum(g * xhat)(C)] with
+// g = dy * (y > 0); a non-null g_out receives g.
 hipError_t BnBwdStatsLaunch(const void* x, const void* y, const void* dy,
                             void* g_out, const float* mean,
                             const float* invstd, long long total, int C,
-                            int dt, float* sum_g, float* sum_gx,
-                            hipStream_t stream);
+                            int dt, float* banks, hipStream_t stream);
+// y == nullptr: dy is the g that BnBwdStatsLaunch materialized, and the pass
+// reads x and g only.
 hipError_t BnBwdApplyLaunch(const void* x, const void* y, const void* dy,
                             void* dx, const float* mean, const float* invstd,
                             const float* gamma, const float* sum_g,

@@ -80,7 +80,7 @@ int main(int argc, char** argv) {
   const double P = (double)total * 2;  // one bf16 pass over the activation
   bench("stats", P, [&] {
     hipMemsetAsync(banks, 0, BANK * sizeof(float), s);
-    BnStatsLaunch(x, total, (int)C, DT_BF16, banks, nullptr, s);
+    BnStatsLaunch(x, total, (int)C, DT_BF16, banks, s);
   });
   BnBankReduceLaunch(banks, (int)C, s);
   BnFinalizeLaunch(banks, params, params + C, nullptr, nullptr, count, 0.1f,
@@ -92,7 +92,7 @@ int main(int argc, char** argv) {
   bench("bwd_stats", 3 * P, [&] {
     hipMemsetAsync(banks2, 0, BANK * sizeof(float), s);
     BnBwdStatsLaunch(x, y, dy, nullptr, params, params + C, total, (int)C,
-                     DT_BF16, banks2, nullptr, s);
+                     DT_BF16, banks2, s);
     BnBankReduceLaunch(banks2, (int)C, s);
   });
   bench("bwd_apply", 4 * P, [&] {

@@ -6,9 +6,27 @@ tf_cnn_benchmarks-style).  torchvision is not available in this image.
 
 MI355X notes: run under channels_last so MIOpen picks NHWC kernels, and in
 bf16 autocast (CDNA4's native matrix dtype).
+
+BatchNorm+ReLU and BatchNorm+Add+ReLU run as the fused HIP kernels of
+horovod_amd.ops.fused_bn by default (`fused_bn=None`): set HOROVOD_FUSED_BN=0
+or pass `fused_bn=False` for stock nn.BatchNorm2d + ReLU.  A `norm_layer`
+other than nn.BatchNorm2d also turns the default off.  The fused modules are
+nn.BatchNorm2d subclasses with the same parameters and state_dict keys, and
+fall back to the stock ops for CPU, eval-mode and non-channels_last inputs.
 """
+import os
+
 import torch
 import torch.nn as nn
+
+
+def _resolve_fused_bn(fused_bn, norm_layer):
+    """fused_bn=None: on for plain BatchNorm2d unless HOROVOD_FUSED_BN=0
+    (read when the model is built)."""
+    if fused_bn is None:
+        return (norm_layer is nn.BatchNorm2d and
+                os.environ.get("HOROVOD_FUSED_BN", "1") != "0")
+    return bool(fused_bn)
 
 
 class Bottleneck(nn.Module):
@@ -52,13 +70,19 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, layers, num_classes=1000, norm_layer=nn.BatchNorm2d,
-                 fused_bn=False):
+                 fused_bn=None):
         super().__init__()
+        fused_bn = _resolve_fused_bn(fused_bn, norm_layer)
         self._norm_layer = norm_layer
         self._fused_bn = fused_bn
         self.in_planes = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
-        self.bn1 = norm_layer(64)
+        if fused_bn:
+            # the stem's 64x112x112 BN+ReLU is the largest one of the model
+            from horovod_amd.ops import FusedBNReLU
+            self.bn1 = FusedBNReLU(64)
+        else:
+            self.bn1 = norm_layer(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
         self.layer1 = self._make_layer(64, layers[0])
@@ -100,7 +124,10 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.bn1(self.conv1(x))
+        if not self._fused_bn:  # FusedBNReLU applies the ReLU itself
+            x = self.relu(x)
+        x = self.maxpool(x)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)
