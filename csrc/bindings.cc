@@ -262,12 +262,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return hvd::gpu::FusedBnReluForward(x, res, gamma, beta, rm, rv,
                                               momentum, eps);
         });
+  // y may be None where beta is given (see FusedBnReluBackward)
   m.def("fused_bn_relu_backward",
-        [](at::Tensor x, at::Tensor y, at::Tensor dy, at::Tensor mean,
-           at::Tensor invstd, at::Tensor gamma, bool need_res) {
-          return hvd::gpu::FusedBnReluBackward(x, y, dy, mean, invstd, gamma,
-                                               need_res);
-        });
+        [](at::Tensor x, py::object y, at::Tensor dy, at::Tensor mean,
+           at::Tensor invstd, at::Tensor gamma, bool need_res,
+           py::object beta) {
+          auto opt = [](const py::object& o) {
+            return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
+          };
+          return hvd::gpu::FusedBnReluBackward(x, opt(y), dy, mean, invstd,
+                                               gamma, need_res, opt(beta));
+        },
+        py::arg("x"), py::arg("y"), py::arg("dy"), py::arg("mean"),
+        py::arg("invstd"), py::arg("gamma"), py::arg("need_residual_grad"),
+        py::arg("beta") = py::none());
+  m.def("fused_bn_lean_path", []() { return hvd::gpu::FusedBnLeanPath(); });
   m.def("fused_bn_pass",
         [](int which, at::Tensor x, py::object a, py::object b, py::object out,
            at::Tensor mean, at::Tensor invstd, at::Tensor gamma,

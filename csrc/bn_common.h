@@ -31,6 +31,23 @@ __device__ __forceinline__ __hip_bfloat16 from_f<__hip_bfloat16>(float v) {
   return __float2bfloat16(v);
 }
 
+// The fused BN+ReLU pre-activation gamma * xhat + beta of one element.  The
+// forward stores relu of it, and the backward passes that do not read y
+// recompute it to learn the ReLU mask, so it has to come out bit-identical
+// in every kernel: each rounding step is spelled out, which leaves the
+// compiler no contraction choice that could differ between them.
+__device__ __forceinline__ float bn_preact(float x, float mean, float invstd,
+                                           float gamma, float beta) {
+  return fmaf(__fmul_rn(__fsub_rn(x, mean), invstd), gamma, beta);
+}
+
+// y > 0 as the forward stored it for pre-activation f (no residual): the
+// round trip through T matters, a positive fp32 f can round to a zero fp16 y
+template <typename T>
+__device__ __forceinline__ bool bn_relu_mask(float f) {
+  return to_f<T>(from_f<T>(f)) > 0.f;
+}
+
 // 8 consecutive elements = one 16-B access for 2-byte types, two for fp32.
 template <typename T>
 union Vec8 {

@@ -14,6 +14,9 @@
 // per array) and partial sums in registers.  Stats accumulate in fp32 via
 // per-block LDS bins (C <= 4096 -> <= 32 KB LDS) flushed with one global
 // atomicAdd per channel per block into kBnBanks partial rows (guide G12).
+// The rows are zero when a reduction starts: they are the stream's persistent
+// workspace, which the kernel that folds them (bn_finalize_k forward,
+// bn_bank_reduce_k backward) zeroes again, or per-call memory with a memset.
 #include "bn_common.h"
 #include "kernels.h"
 
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(256) void bn_apply_relu_k(
     if (ADD) load8(vr, res, i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float f = (to_f<T>(vx.e[k]) - rm[k]) * ri[k] * rg[k] + rb[k];
+      float f = bn_preact(to_f<T>(vx.e[k]), rm[k], ri[k], rg[k], rb[k]);
       if (ADD) f += to_f<T>(vr.e[k]);
       vy.e[k] = from_f<T>(f > 0.f ? f : 0.f);
     }
@@ -104,11 +107,14 @@ __global__ __launch_bounds__(256) void bn_apply_relu_k(
 
 // ---- backward stats: g = dy*(y>0); per-channel sum(g), sum(g*xhat);
 //      optionally materialize g (residual gradient for the ADD variant)
-template <typename T, bool WRITE_G>
+// FROM_X (no residual only): y is not read; y > 0 is recomputed from x and
+// the layer's mean, invstd, gamma and beta (bn_preact, bn_relu_mask).
+template <typename T, bool WRITE_G, bool FROM_X>
 __global__ __launch_bounds__(256) void bn_bwd_stats_k(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
     T* __restrict__ g_out, const float* __restrict__ mean,
-    const float* __restrict__ invstd, long long total, int C,
+    const float* __restrict__ invstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, long long total, int C,
     float* __restrict__ banks) {
   extern __shared__ float lds[];  // [C] sum(g), [C] sum(g * xhat)
   for (int c = threadIdx.x; c < 2 * C; c += blockDim.x) lds[c] = 0.f;
@@ -121,78 +127,110 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_k(
   // after the loop, which keeps 8 registers out of it
   float rmean[8], racc_g[8] = {0}, racc_gx[8] = {0};
   load_octet(rmean, mean, c0, 0.f);
+  float rinv[8], rg[8], rb[8];
+  if (FROM_X) {
+    load_octet(rinv, invstd, c0, 0.f);
+    load_octet(rg, gamma, c0, 1.f);
+    load_octet(rb, beta, c0, 0.f);
+  }
   // One vector of each of the three tensors in flight per thread.  Two of
   // each took 102-128 VGPRs (4 waves/SIMD against 6-7 here), and holding
   // that form to 7 waves spilled 156-188 B/lane to scratch.
   for (long long i = tid; i < nvec; i += nthreads) {
     Vec8<T> vx, vy, vd, vg;
     load8(vx, x, i);
-    load8(vy, y, i);
+    if (!FROM_X) load8(vy, y, i);
     load8(vd, dy, i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float gv = to_f<T>(vy.e[k]) > 0.f ? to_f<T>(vd.e[k]) : 0.f;
+      const float xf = to_f<T>(vx.e[k]);
+      const bool on =
+          FROM_X ? bn_relu_mask<T>(bn_preact(xf, rmean[k], rinv[k], rg[k], rb[k]))
+                 : to_f<T>(vy.e[k]) > 0.f;
+      float gv = on ? to_f<T>(vd.e[k]) : 0.f;
       racc_g[k] += gv;
-      racc_gx[k] += gv * (to_f<T>(vx.e[k]) - rmean[k]);
+      racc_gx[k] += gv * (xf - rmean[k]);
       if (WRITE_G) vg.e[k] = from_f<T>(gv);
     }
     if (WRITE_G) store8(g_out, i, vg);
   }
-  float rinv[8];
-  load_octet(rinv, invstd, c0, 0.f);
+  if (!FROM_X) load_octet(rinv, invstd, c0, 0.f);
 #pragma unroll
   for (int k = 0; k < 8; ++k) racc_gx[k] *= rinv[k];
   octet_flush(racc_g, racc_gx, c0, C, lds, banks);
 }
 
-// reduce the kBnBanks x [2C] partials into banks[0] (the backward tail)
+// reduce the kBnBanks x [2C] partials into sums[2C] (the backward tail).
+// CLEAR: the banks are the stream's persistent workspace, and every word
+// read is zeroed again for the next reduction.
+template <bool CLEAR>
 __global__ __launch_bounds__(256) void bn_bank_reduce_k(float* banks,
-                                                        int C) {
+                                                        float* sums, int C) {
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < 2 * C;
        c += gridDim.x * blockDim.x) {
     float acc = 0.f;
     for (int b = 0; b < kBnBanks; ++b) acc += banks[(size_t)b * 2 * C + c];
-    banks[c] = acc;
+    // all loads first: a store in between would order them one by one
+    if (CLEAR)
+      for (int b = 0; b < kBnBanks; ++b) banks[(size_t)b * 2 * C + c] = 0.f;
+    sums[c] = acc;
   }
 }
 
 // ---- backward apply: dx = gamma*invstd*(g - sum_g/n - xhat*sum_gx/n) ------
 // FROM_G: `dy` is the g = dy*(y>0) that bn_bwd_stats_k<WRITE_G> stored
 // (exact: each element is dy itself or 0), so y is not read at all.
-template <typename T, bool FROM_G>
+// FROM_X (no residual only): y is not read either; y > 0 is recomputed from
+// x as in bn_bwd_stats_k<FROM_X>.  That variant keeps gamma in registers for
+// the pre-activation and forms gamma * invstd per element (the same rounded
+// product) instead of holding a sixth per-channel array.
+template <typename T, bool FROM_G, bool FROM_X>
 __global__ __launch_bounds__(256) void bn_bwd_apply_k(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
     T* __restrict__ dx, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ gamma,
-    const float* __restrict__ sum_g, const float* __restrict__ sum_gx,
-    long long total, int C, float inv_count) {
+    const float* __restrict__ beta, const float* __restrict__ sum_g,
+    const float* __restrict__ sum_gx, long long total, int C,
+    float inv_count) {
+  static_assert(!(FROM_G && FROM_X), "one source of the ReLU mask");
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long nthreads = (long long)gridDim.x * blockDim.x;
   const long long nvec = total / 8;
   const int c0 = octet_channel(C);
-  float rmean[8], rinv[8], rgi[8], rsg[8], rsgx[8];
+  float rmean[8], rinv[8], rgi[8], rsg[8], rsgx[8], rb[8];
   load_octet(rmean, mean, c0, 0.f);
   load_octet(rinv, invstd, c0, 0.f);
   load_octet(rgi, gamma, c0, 1.f);
   load_octet(rsg, sum_g, c0, 0.f);
   load_octet(rsgx, sum_gx, c0, 0.f);
+  if (FROM_X) load_octet(rb, beta, c0, 0.f);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    rgi[k] = rgi[k] * rinv[k];
+    if (!FROM_X) rgi[k] = rgi[k] * rinv[k];  // FROM_X: rgi stays gamma
     rsg[k] = rsg[k] * inv_count;
     rsgx[k] = rsgx[k] * inv_count;
   }
   for (long long i = tid; i < nvec; i += nthreads) {
     Vec8<T> vx, vy, vd, vo;
     load8(vx, x, i);
-    if (!FROM_G) load8(vy, y, i);
+    if (!FROM_G && !FROM_X) load8(vy, y, i);
     load8(vd, dy, i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float gv = FROM_G ? to_f<T>(vd.e[k])
-                        : (to_f<T>(vy.e[k]) > 0.f ? to_f<T>(vd.e[k]) : 0.f);
-      float xh = (to_f<T>(vx.e[k]) - rmean[k]) * rinv[k];
-      float v = rgi[k] * (gv - rsg[k] - xh * rsgx[k]);
+      const float xf = to_f<T>(vx.e[k]);
+      float gv;
+      if (FROM_G) {
+        gv = to_f<T>(vd.e[k]);
+      } else {
+        const bool on =
+            FROM_X ? bn_relu_mask<T>(
+                         bn_preact(xf, rmean[k], rinv[k], rgi[k], rb[k]))
+                   : to_f<T>(vy.e[k]) > 0.f;
+        gv = on ? to_f<T>(vd.e[k]) : 0.f;
+      }
+      float xh = (xf - rmean[k]) * rinv[k];
+      const float gi = FROM_X ? rgi[k] * rinv[k] : rgi[k];
+      float v = gi * (gv - rsg[k] - xh * rsgx[k]);
       vo.e[k] = from_f<T>(v);
     }
     store8(dx, i, vo);
@@ -202,8 +240,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(
 // ---- forward epilogue: fold the banks, mean/invstd, running stats ---------
 // One thread per channel over (C + 255) / 256 blocks; the 2 x kBnBanks loads
 // of a thread are independent and coalesced across the block.
+// CLEAR: the banks are the stream's persistent workspace; the threads
+// together read every word of its kBnBanks x [2C] rows, and each zeroes what
+// it read for the next reduction.  mean / invstd never alias the banks then.
+template <bool CLEAR>
 __global__ __launch_bounds__(256) void bn_finalize_k(
-    const float* __restrict__ banks, float* __restrict__ mean,
+    float* __restrict__ banks, float* __restrict__ mean,
     float* __restrict__ invstd, float* __restrict__ running_mean,
     float* __restrict__ running_var, long long count, float momentum,
     float eps, int C) {
@@ -216,6 +258,13 @@ __global__ __launch_bounds__(256) void bn_finalize_k(
   for (int b = 0; b < kBnBanks; ++b) {
     s += banks[(size_t)b * 2 * C + c];
     q += banks[(size_t)b * 2 * C + C + c];
+  }
+  if (CLEAR) {
+#pragma unroll 16
+    for (int b = 0; b < kBnBanks; ++b) {
+      banks[(size_t)b * 2 * C + c] = 0.f;
+      banks[(size_t)b * 2 * C + C + c] = 0.f;
+    }
   }
   float m = s * inv_n;
   float v = q * inv_n - m * m;
@@ -243,18 +292,31 @@ bool aligned16(const void* const (&ptrs)[N]) {
     default: return hipErrorInvalidValue;                         \
   }
 
-hipError_t BnFinalizeLaunch(const float* banks, float* mean, float* invstd,
+hipError_t BnFinalizeLaunch(float* banks, float* mean, float* invstd,
                             float* running_mean, float* running_var,
                             long long count, float momentum, float eps,
-                            int C, hipStream_t stream) {
-  bn_finalize_k<<<(C + 255) / 256, 256, 0, stream>>>(
-      banks, mean, invstd, running_mean, running_var, count, momentum, eps, C);
+                            int C, bool clear_banks, hipStream_t stream) {
+  const int blocks = (C + 255) / 256;
+  if (clear_banks)
+    bn_finalize_k<true><<<blocks, 256, 0, stream>>>(
+        banks, mean, invstd, running_mean, running_var, count, momentum, eps,
+        C);
+  else
+    bn_finalize_k<false><<<blocks, 256, 0, stream>>>(
+        banks, mean, invstd, running_mean, running_var, count, momentum, eps,
+        C);
   return hipGetLastError();
 }
 
-hipError_t BnBankReduceLaunch(float* banks, int C, hipStream_t stream) {
+hipError_t BnBankReduceLaunch(float* banks, float* sums, int C,
+                              bool clear_banks, hipStream_t stream) {
+  const void* const ptrs[] = {sums};
+  if (!aligned16(ptrs)) return hipErrorInvalidValue;
   int blocks = (2 * C + 255) / 256;
-  bn_bank_reduce_k<<<blocks, 256, 0, stream>>>(banks, C);
+  if (clear_banks)
+    bn_bank_reduce_k<true><<<blocks, 256, 0, stream>>>(banks, sums, C);
+  else
+    bn_bank_reduce_k<false><<<blocks, 256, 0, stream>>>(banks, sums, C);
   return hipGetLastError();
 }
 
@@ -292,45 +354,64 @@ hipError_t BnApplyReluLaunch(const void* x, const void* res, void* y,
 
 hipError_t BnBwdStatsLaunch(const void* x, const void* y, const void* dy,
                             void* g_out, const float* mean,
-                            const float* invstd, long long total, int C,
-                            int dt, float* banks, hipStream_t stream) {
-  const void* const ptrs[] = {x, y, dy, g_out, mean, invstd};
+                            const float* invstd, const float* gamma,
+                            const float* beta, long long total, int C, int dt,
+                            float* banks, hipStream_t stream) {
+  const void* const ptrs[] = {x, y, dy, g_out, mean, invstd, gamma, beta};
   if (!aligned16(ptrs)) return hipErrorInvalidValue;
+  // the mask comes from y, or without a residual from x, gamma and beta
+  if (beta ? (g_out != nullptr || !gamma) : !y) return hipErrorInvalidValue;
   int blocks = vec8_reduce_grid(total, C);
   size_t lds = 2 * (size_t)C * sizeof(float);
-  if (g_out) {
-    DISPATCH_T(dt,
-               (bn_bwd_stats_k<scalar_t, true><<<blocks, 256, lds, stream>>>(
-                   (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
-                   (scalar_t*)g_out, mean, invstd, total, C, banks)));
+  if (beta) {
+    DISPATCH_T(
+        dt, (bn_bwd_stats_k<scalar_t, false, true><<<blocks, 256, lds, stream>>>(
+                (const scalar_t*)x, nullptr, (const scalar_t*)dy, nullptr, mean,
+                invstd, gamma, beta, total, C, banks)));
+  } else if (g_out) {
+    DISPATCH_T(
+        dt, (bn_bwd_stats_k<scalar_t, true, false><<<blocks, 256, lds, stream>>>(
+                (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
+                (scalar_t*)g_out, mean, invstd, nullptr, nullptr, total, C,
+                banks)));
   } else {
-    DISPATCH_T(dt,
-               (bn_bwd_stats_k<scalar_t, false><<<blocks, 256, lds, stream>>>(
-                   (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
-                   nullptr, mean, invstd, total, C, banks)));
+    DISPATCH_T(
+        dt,
+        (bn_bwd_stats_k<scalar_t, false, false><<<blocks, 256, lds, stream>>>(
+            (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
+            nullptr, mean, invstd, nullptr, nullptr, total, C, banks)));
   }
   return hipGetLastError();
 }
 
 hipError_t BnBwdApplyLaunch(const void* x, const void* y, const void* dy,
                             void* dx, const float* mean, const float* invstd,
-                            const float* gamma, const float* sum_g,
-                            const float* sum_gx, long long total, int C,
-                            int dt, float inv_count, hipStream_t stream) {
-  const void* const ptrs[] = {x,      y,     dy,    dx,    mean,
-                              invstd, gamma, sum_g, sum_gx};
+                            const float* gamma, const float* beta,
+                            const float* sum_g, const float* sum_gx,
+                            long long total, int C, int dt, float inv_count,
+                            hipStream_t stream) {
+  const void* const ptrs[] = {x,     y,    dy,    dx,    mean, invstd,
+                              gamma, beta, sum_g, sum_gx};
   if (!aligned16(ptrs)) return hipErrorInvalidValue;
   int blocks = grid_for(total, C);
-  if (y) {
-    DISPATCH_T(dt, (bn_bwd_apply_k<scalar_t, false><<<blocks, 256, 0, stream>>>(
-                       (const scalar_t*)x, (const scalar_t*)y,
-                       (const scalar_t*)dy, (scalar_t*)dx, mean, invstd, gamma,
-                       sum_g, sum_gx, total, C, inv_count)));
+  if (beta) {
+    DISPATCH_T(
+        dt, (bn_bwd_apply_k<scalar_t, false, true><<<blocks, 256, 0, stream>>>(
+                (const scalar_t*)x, nullptr, (const scalar_t*)dy,
+                (scalar_t*)dx, mean, invstd, gamma, beta, sum_g, sum_gx, total,
+                C, inv_count)));
+  } else if (y) {
+    DISPATCH_T(
+        dt, (bn_bwd_apply_k<scalar_t, false, false><<<blocks, 256, 0, stream>>>(
+                (const scalar_t*)x, (const scalar_t*)y, (const scalar_t*)dy,
+                (scalar_t*)dx, mean, invstd, gamma, nullptr, sum_g, sum_gx,
+                total, C, inv_count)));
   } else {
-    DISPATCH_T(dt, (bn_bwd_apply_k<scalar_t, true><<<blocks, 256, 0, stream>>>(
-                       (const scalar_t*)x, nullptr, (const scalar_t*)dy,
-                       (scalar_t*)dx, mean, invstd, gamma, sum_g, sum_gx,
-                       total, C, inv_count)));
+    DISPATCH_T(
+        dt, (bn_bwd_apply_k<scalar_t, true, false><<<blocks, 256, 0, stream>>>(
+                (const scalar_t*)x, nullptr, (const scalar_t*)dy,
+                (scalar_t*)dx, mean, invstd, gamma, nullptr, sum_g, sum_gx,
+                total, C, inv_count)));
   }
   return hipGetLastError();
 }

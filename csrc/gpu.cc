@@ -1543,7 +1543,94 @@ at::Tensor BnParamF32(const at::Tensor& t) {
   return t.to(at::kFloat).clone(at::MemoryFormat::Contiguous);
 }
 
+// HOROVOD_FUSED_BN_WORKSPACE=0, read once: every call allocates and memsets
+// its own banks and the backward always reads y (the path before the
+// persistent workspace; for A/B runs and as an escape hatch).
+bool BnLeanPath() {
+  static const bool on = [] {
+    const char* v = std::getenv("HOROVOD_FUSED_BN_WORKSPACE");
+    return !(v && v[0] == '0' && v[1] == '\0');
+  }();
+  return on;
+}
+
+// One persistent bank workspace per (device, stream), sized for the widest
+// layer and allocated zeroed on first use.  Invariant: all of it is zero
+// whenever no fused-BN call on that stream is between its reduction launch
+// and its consumer launch (bn_finalize_k / bn_bank_reduce_k with clear_banks
+// zero every word the reduction can have touched).  `mu` is held over that
+// pair of launches, so two host threads on one stream cannot interleave
+// theirs.  Slots are never freed: nothing here runs at interpreter or
+// runtime teardown.
+struct BnBankSlot {
+  std::mutex mu;
+  at::Tensor banks;
+};
+
+BnBankSlot* BnSlot(int device, hipStream_t stream) {
+  static std::mutex mu;
+  static auto* slots = new std::unordered_map<uint64_t, std::unordered_map<
+                           hipStream_t, BnBankSlot*>>();
+  std::lock_guard<std::mutex> lock(mu);
+  BnBankSlot*& slot = (*slots)[(uint64_t)device][stream];
+  if (!slot) slot = new BnBankSlot();
+  return slot;
+}
+
+// The zeroed banks of one reduction -> consumer pair.  Normally the stream's
+// workspace; on a capturing stream, or with the switch off, a per-call
+// buffer plus memset: a capture must not allocate outside its pool, and a
+// graph must not keep a pointer to a workspace that can be dropped (below)
+// or race with eager calls on the stream it is replayed on.
+class BnBankLease {
+ public:
+  BnBankLease(int device, hipStream_t stream, int64_t C,
+              const at::TensorOptions& fopts) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (BnLeanPath()) HIP_CHECK(hipStreamIsCapturing(stream, &st));
+    if (BnLeanPath() && st == hipStreamCaptureStatusNone) {
+      slot_ = BnSlot(device, stream);
+      lock_ = std::unique_lock<std::mutex>(slot_->mu);
+      if (!slot_->banks.defined())
+        slot_->banks =
+            at::zeros({(int64_t)kBnBanks * 2 * kBnMaxChannels}, fopts);
+      banks_ = slot_->banks.data_ptr<float>();
+    } else {
+      own_ = at::empty({(int64_t)kBnBanks * 2 * C}, fopts);
+      banks_ = own_.data_ptr<float>();
+      HIP_CHECK(hipMemsetAsync(banks_, 0,
+                               (size_t)kBnBanks * 2 * C * sizeof(float),
+                               stream));
+    }
+  }
+  // A launch between the reduction and its consumer failed: the banks may
+  // be dirty, so the stream's workspace is dropped and the next call
+  // allocates a zeroed one.
+  ~BnBankLease() {
+    if (slot_ && !consumed_) slot_->banks = at::Tensor();
+  }
+  BnBankLease(const BnBankLease&) = delete;
+  BnBankLease& operator=(const BnBankLease&) = delete;
+
+  float* banks() const { return banks_; }
+  bool persistent() const { return slot_ != nullptr; }
+  // the consumer launch went through: the banks are zero again
+  void Consumed() {
+    consumed_ = true;
+    if (lock_.owns_lock()) lock_.unlock();
+  }
+
+ private:
+  BnBankSlot* slot_ = nullptr;
+  std::unique_lock<std::mutex> lock_;
+  at::Tensor own_;
+  float* banks_ = nullptr;
+  bool consumed_ = false;
+};
+
 }  // namespace
+
+bool FusedBnLeanPath() { return BnLeanPath(); }
 
 // Returns {y, save_mean, save_invstd}.  Small per-channel math ([C] tensors)
 // runs through ATen; the big passes are the CDNA4 kernels.
@@ -1572,19 +1659,10 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
   int dt = (int)DataTypeFromTorch(x.scalar_type());
 
   auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
-  // one workspace, zero ATen math on [C] tensors: the per-channel epilogue
-  // (mean/invstd + running-stat update) runs in bn_finalize_k — the
-  // previous ~10 tiny ATen launches per BN layer cost 3.5 ms/step of pure
-  // launch overhead at batch 64 (53 layers, fwd+bwd)
-  // mean / invstd sit behind the banks, 16-B aligned because C % 8 == 0
-  const int64_t bank_elems = (int64_t)kBnBanks * 2 * C;
-  at::Tensor ws = at::empty({bank_elems + 2 * C}, fopts);
-  float* wsp = ws.data_ptr<float>();
-  float* mean_p = wsp + bank_elems;
-  float* invstd_p = mean_p + C;
-  HIP_CHECK(hipMemsetAsync(wsp, 0, (size_t)bank_elems * sizeof(float),
-                           stream));
-  HIP_CHECK(BnStatsLaunch(x.data_ptr(), total, (int)C, dt, wsp, stream));
+  // zero ATen math on [C] tensors: the per-channel epilogue (mean/invstd +
+  // running-stat update) runs in bn_finalize_k — the previous ~10 tiny ATen
+  // launches per BN layer cost 3.5 ms/step of pure launch overhead at batch
+  // 64 (53 layers, fwd+bwd)
   // running stats may sit at any offset: bn_finalize_k reads them per channel
   TORCH_CHECK(!running_mean.defined() ||
                   (running_var.defined() && running_mean.numel() == C &&
@@ -1595,13 +1673,24 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
                    running_mean.is_contiguous() &&
                    running_var.scalar_type() == at::kFloat &&
                    running_var.is_contiguous();
+  // mean / invstd are the halves of one [2C] tensor, 16-B aligned because
+  // C % 8 == 0; they never live in the banks, which other layers reuse
+  at::Tensor stats = at::empty({2 * C}, fopts);
+  float* mean_p = stats.data_ptr<float>();
+  float* invstd_p = mean_p + C;
+  // nothing but the two launches between taking the banks and handing them
+  // back clean
+  BnBankLease lease(device, stream, C, fopts);
+  HIP_CHECK(
+      BnStatsLaunch(x.data_ptr(), total, (int)C, dt, lease.banks(), stream));
   HIP_CHECK(BnFinalizeLaunch(
-      wsp, mean_p, invstd_p,
+      lease.banks(), mean_p, invstd_p,
       stats_f32 ? running_mean.data_ptr<float>() : nullptr,
       stats_f32 ? running_var.data_ptr<float>() : nullptr, count,
-      (float)momentum, (float)eps, (int)C, stream));
-  at::Tensor mean = ws.narrow(0, bank_elems, C);
-  at::Tensor invstd = ws.narrow(0, bank_elems + C, C);
+      (float)momentum, (float)eps, (int)C, lease.persistent(), stream));
+  lease.Consumed();
+  at::Tensor mean = stats.narrow(0, 0, C);
+  at::Tensor invstd = stats.narrow(0, C, C);
   if (!stats_f32 && running_mean.defined()) {
     // rare non-fp32 running stats: fall back to ATen for the update only
     at::Tensor var = at::pow(invstd, -2) - eps;
@@ -1621,11 +1710,15 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
   return {y, mean, invstd};
 }
 
-// Returns {dx, dgamma, dbeta[, dresidual]}.
+// Returns {dx, dgamma, dbeta[, dresidual]}.  With beta given and no residual
+// gradient wanted (a layer without a residual), y is not read and may be
+// undefined: the ReLU mask is recomputed from x (bn_kernels.hip, FROM_X).
+// HOROVOD_FUSED_BN_WORKSPACE=0 turns that off, and y is needed again.
 std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
                                             at::Tensor dy, at::Tensor mean,
                                             at::Tensor invstd, at::Tensor gamma,
-                                            bool need_residual_grad) {
+                                            bool need_residual_grad,
+                                            at::Tensor beta) {
   int device = (int)x.get_device();
   c10::hip::HIPGuard guard(device);
   hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
@@ -1633,45 +1726,60 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
   int64_t total = x.numel();
   int64_t count = total / C;
   int dt = (int)DataTypeFromTorch(x.scalar_type());
+  const bool from_x = beta.defined() && !need_residual_grad && BnLeanPath();
   if (!dy.is_contiguous(at::MemoryFormat::ChannelsLast))
     dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(from_x || y.defined(),
+              "fused BN backward: y is needed unless beta is given, no "
+              "residual gradient is wanted and HOROVOD_FUSED_BN_WORKSPACE "
+              "is not 0");
   TORCH_CHECK(x.dim() == 4 && C % 8 == 0 && C <= 4096 &&
                   x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  y.is_contiguous(at::MemoryFormat::ChannelsLast),
+                  (from_x || y.is_contiguous(at::MemoryFormat::ChannelsLast)),
               "fused BN backward: x and y must be channels_last with "
               "C % 8 == 0, C <= 4096");
-  TORCH_CHECK(y.sizes() == x.sizes() && dy.sizes() == x.sizes() &&
-                  y.scalar_type() == x.scalar_type() &&
+  TORCH_CHECK((from_x || (y.sizes() == x.sizes() &&
+                          y.scalar_type() == x.scalar_type())) &&
+                  dy.sizes() == x.sizes() &&
                   dy.scalar_type() == x.scalar_type() &&
                   mean.numel() == C && invstd.numel() == C &&
-                  gamma.numel() == C,
+                  gamma.numel() == C && (!from_x || beta.numel() == C),
               "fused BN backward: mismatched shapes or dtypes");
 
   auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
-  at::Tensor sums = at::empty({(int64_t)kBnBanks * 2 * C}, fopts);
-  float* bankp = sums.data_ptr<float>();
-  HIP_CHECK(hipMemsetAsync(bankp, 0,
-                           (size_t)kBnBanks * 2 * C * sizeof(float), stream));
+  // [sum(g), sum(g * xhat)]: feeds the apply pass and is returned as dbeta /
+  // dgamma, so it is a tensor of this call and never part of the banks
+  at::Tensor sums = at::empty({2 * C}, fopts);
+  float* sump = sums.data_ptr<float>();
   at::Tensor dres;
   if (need_residual_grad) dres = at::empty_like(x);
-  // the forward's own mean / invstd are aligned views of its workspace
+  // the forward's own mean / invstd are aligned halves of one tensor
   at::Tensor mean_f = BnParamF32(mean), invstd_f = BnParamF32(invstd);
-  HIP_CHECK(BnBwdStatsLaunch(x.data_ptr(), y.data_ptr(), dy.data_ptr(),
-                             need_residual_grad ? dres.data_ptr() : nullptr,
-                             mean_f.data_ptr<float>(),
-                             invstd_f.data_ptr<float>(), total, (int)C, dt,
-                             bankp, stream));
-  HIP_CHECK(BnBankReduceLaunch(bankp, (int)C, stream));
-  at::Tensor gamma_f = BnParamF32(gamma);
+  // the same fp32 copies the forward made, where it had to make any
+  at::Tensor gamma_f = BnParamF32(gamma), beta_f;
+  if (from_x) beta_f = BnParamF32(beta);
+  const float* gamma_p = gamma_f.data_ptr<float>();
+  const float* beta_p = from_x ? beta_f.data_ptr<float>() : nullptr;
   at::Tensor dx = at::empty_like(x);
+  {
+    BnBankLease lease(device, stream, C, fopts);
+    HIP_CHECK(BnBwdStatsLaunch(
+        x.data_ptr(), from_x ? nullptr : y.data_ptr(), dy.data_ptr(),
+        need_residual_grad ? dres.data_ptr() : nullptr,
+        mean_f.data_ptr<float>(), invstd_f.data_ptr<float>(),
+        from_x ? gamma_p : nullptr, beta_p, total, (int)C, dt, lease.banks(),
+        stream));
+    HIP_CHECK(BnBankReduceLaunch(lease.banks(), sump, (int)C,
+                                 lease.persistent(), stream));
+    lease.Consumed();
+  }
   // Add variant: dres already holds g = dy * (y > 0) exactly, so the apply
   // pass reads it and x instead of x, y and dy
   HIP_CHECK(BnBwdApplyLaunch(
-      x.data_ptr(), need_residual_grad ? nullptr : y.data_ptr(),
+      x.data_ptr(), (need_residual_grad || from_x) ? nullptr : y.data_ptr(),
       need_residual_grad ? dres.data_ptr() : dy.data_ptr(), dx.data_ptr(),
-      mean_f.data_ptr<float>(), invstd_f.data_ptr<float>(),
-      gamma_f.data_ptr<float>(), bankp, bankp + C, total, (int)C, dt,
-      (float)(1.0 / count), stream));
+      mean_f.data_ptr<float>(), invstd_f.data_ptr<float>(), gamma_p, beta_p,
+      sump, sump + C, total, (int)C, dt, (float)(1.0 / count), stream));
   at::Tensor sum_g = sums.narrow(0, 0, C), sum_gx = sums.narrow(0, C, C);
   at::Tensor dbeta = gamma.scalar_type() == at::kFloat
                          ? sum_g
@@ -1692,6 +1800,8 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
 //   0 stats(x)                      1 apply(x, res = a or none) -> out
 //   2 bwd stats(x, y = a, dy = b) [-> g = out]
 //   3 bwd apply(x, y = a or none, dy or g = b) -> out
+//   4 bwd stats(x, dy = b), mask recomputed from x
+//   5 bwd apply(x, dy = b) -> out, mask recomputed from x
 void FusedBnPass(int which, at::Tensor x, at::Tensor a, at::Tensor b,
                  at::Tensor out, at::Tensor mean, at::Tensor invstd,
                  at::Tensor gamma, at::Tensor beta) {
@@ -1740,8 +1850,8 @@ void FusedBnPass(int which, at::Tensor x, at::Tensor a, at::Tensor b,
       TORCH_CHECK(a.defined() && b.defined(), "fused BN pass 2 needs y, dy");
       HIP_CHECK(hipMemsetAsync(bankp, 0, bank_bytes, stream));
       HIP_CHECK(BnBwdStatsLaunch(x.data_ptr(), a.data_ptr(), b.data_ptr(),
-                                 ptr(out), mp, ip, total, (int)C, dt, bankp,
-                                 stream));
+                                 ptr(out), mp, ip, nullptr, nullptr, total,
+                                 (int)C, dt, bankp, stream));
       break;
     case 3:
       TORCH_CHECK(b.defined() && out.defined(),
@@ -1749,12 +1859,30 @@ void FusedBnPass(int which, at::Tensor x, at::Tensor a, at::Tensor b,
       // the sums' values do not matter to the timing; mean stands in
       HIP_CHECK(BnBwdApplyLaunch(x.data_ptr(), ptr(a), b.data_ptr(),
                                  out.data_ptr(), mp, ip,
-                                 gamma.data_ptr<float>(), mp, ip, total,
+                                 gamma.data_ptr<float>(), nullptr, mp, ip,
+                                 total, (int)C, dt,
+                                 1.0f / (float)(total / C), stream));
+      break;
+    case 4:
+      TORCH_CHECK(b.defined(), "fused BN pass 4 needs dy");
+      HIP_CHECK(hipMemsetAsync(bankp, 0, bank_bytes, stream));
+      HIP_CHECK(BnBwdStatsLaunch(x.data_ptr(), nullptr, b.data_ptr(), nullptr,
+                                 mp, ip, gamma.data_ptr<float>(),
+                                 beta.data_ptr<float>(), total, (int)C, dt,
+                                 bankp, stream));
+      break;
+    case 5:
+      TORCH_CHECK(b.defined() && out.defined(),
+                  "fused BN pass 5 needs dy and out");
+      HIP_CHECK(BnBwdApplyLaunch(x.data_ptr(), nullptr, b.data_ptr(),
+                                 out.data_ptr(), mp, ip,
+                                 gamma.data_ptr<float>(),
+                                 beta.data_ptr<float>(), mp, ip, total,
                                  (int)C, dt, 1.0f / (float)(total / C),
                                  stream));
       break;
     default:
-      TORCH_CHECK(false, "fused BN pass: which must be 0..3");
+      TORCH_CHECK(false, "fused BN pass: which must be 0..5");
   }
 }
 

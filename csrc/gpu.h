@@ -56,7 +56,9 @@ bool RcclUsed();
 void AdasumCombine(std::vector<at::Tensor>& a, std::vector<at::Tensor>& b);
 
 // Fused BatchNorm(+Add)+ReLU (training forward + backward); see
-// bn_kernels.hip.  residual may be undefined.
+// bn_kernels.hip.  residual may be undefined.  With beta defined and no
+// residual gradient wanted, the backward does not read y (it may be
+// undefined): the ReLU mask is recomputed from x.
 std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
                                            at::Tensor gamma, at::Tensor beta,
                                            at::Tensor running_mean,
@@ -65,10 +67,15 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
 std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
                                             at::Tensor dy, at::Tensor mean,
                                             at::Tensor invstd, at::Tensor gamma,
-                                            bool need_residual_grad);
+                                            bool need_residual_grad,
+                                            at::Tensor beta = at::Tensor());
+// False when HOROVOD_FUSED_BN_WORKSPACE=0 selected the per-call banks with
+// their memset and the y-reading backward for this process.
+bool FusedBnLeanPath();
 // One big pass of the fused path on its own (per-pass timing probe):
-// which = 0 stats, 1 apply, 2 backward stats, 3 backward apply; a / b / out
-// may be undefined where the pass has no such tensor (see gpu.cc).
+// which = 0 stats, 1 apply, 2 backward stats, 3 backward apply, 4 / 5 the
+// backward passes that recompute the ReLU mask from x; a / b / out may be
+// undefined where the pass has no such tensor (see gpu.cc).
 void FusedBnPass(int which, at::Tensor x, at::Tensor a, at::Tensor b,
                  at::Tensor out, at::Tensor mean, at::Tensor invstd,
                  at::Tensor gamma, at::Tensor beta);

@@ -353,9 +353,11 @@ hipError_t LarsUpdateMasterLaunch(const LarsMasterBatchArgs& args, int dt,
 // dt in {DT_F32, DT_F16, DT_BF16}; stats/params fp32.
 //
 // The reduction kernels flush block partials into kBnBanks rows of [2*C]
-// floats (zeroed by the caller): one shared accumulator serializes at the
-// memory controller under thousands of blocks.
+// floats (all zero when the reduction starts): one shared accumulator
+// serializes at the memory controller under thousands of blocks.
 constexpr int kBnBanks = 64;
+// widest layer the fused path takes; sizes the persistent bank workspace
+constexpr int kBnMaxChannels = 4096;
 
 // Every activation pointer and per-channel fp32 array below is read as 16-B
 // vectors; a launcher returns hipErrorInvalidValue for one that is not 16-B
@@ -369,12 +371,17 @@ hipError_t BnStatsLaunch(const void* x, long long total, int C, int dt,
 // Per-channel forward epilogue in ONE multi-block kernel: fold the banks +
 // mean/invstd + running stats.  Replaces ~10 tiny ATen launches per BN layer
 // (measured 3.5 ms/step of pure launch overhead at batch 64).
-hipError_t BnFinalizeLaunch(const float* banks, float* mean, float* invstd,
+// clear_banks: also write zero to every bank word read (all kBnBanks * 2 * C
+// of them), which leaves a persistent workspace ready for the next reduction
+// without a memset; mean / invstd must then lie outside the banks.
+hipError_t BnFinalizeLaunch(float* banks, float* mean, float* invstd,
                             float* running_mean, float* running_var,
                             long long count, float momentum, float eps,
-                            int C, hipStream_t stream);
-// Reduce banks into banks[0..2C) (the bwd tail; fwd folds it into finalize).
-hipError_t BnBankReduceLaunch(float* banks, int C, hipStream_t stream);
+                            int C, bool clear_banks, hipStream_t stream);
+// Reduce banks into sums[0..2C) (the bwd tail; fwd folds it into finalize).
+// clear_banks as above; sums lies outside the banks.
+hipError_t BnBankReduceLaunch(float* banks, float* sums, int C,
+                              bool clear_banks, hipStream_t stream);
 hipError_t BnApplyReluLaunch(const void* x, const void* res, void* y,
                              const float* mean, const float* invstd,
                              const float* gamma, const float* beta,
@@ -382,17 +389,23 @@ hipError_t BnApplyReluLaunch(const void* x, const void* res, void* y,
                              hipStream_t stream);
 // banks as in BnStatsLaunch, rows of [sum(g)(C), sum(g * xhat)(C)] with
 // g = dy * (y > 0); a non-null g_out receives g.
+// beta != nullptr (layers without a residual; needs gamma, no g_out): y is
+// not read, and y > 0 is recomputed bit-exactly from x, mean, invstd, gamma
+// and beta as BnApplyReluLaunch stored it.  Otherwise gamma is not read.
 hipError_t BnBwdStatsLaunch(const void* x, const void* y, const void* dy,
                             void* g_out, const float* mean,
-                            const float* invstd, long long total, int C,
-                            int dt, float* banks, hipStream_t stream);
+                            const float* invstd, const float* gamma,
+                            const float* beta, long long total, int C, int dt,
+                            float* banks, hipStream_t stream);
+// beta != nullptr: as above, the pass reads x and dy only.  Otherwise
 // y == nullptr: dy is the g that BnBwdStatsLaunch materialized, and the pass
 // reads x and g only.
 hipError_t BnBwdApplyLaunch(const void* x, const void* y, const void* dy,
                             void* dx, const float* mean, const float* invstd,
-                            const float* gamma, const float* sum_g,
-                            const float* sum_gx, long long total, int C,
-                            int dt, float inv_count, hipStream_t stream);
+                            const float* gamma, const float* beta,
+                            const float* sum_g, const float* sum_gx,
+                            long long total, int C, int dt, float inv_count,
+                            hipStream_t stream);
 
 // ---- SyncBatchNorm (syncbn_kernels.hip) ------------------------------------
 // Activations are a dense (outer, C, inner) block: planar (N, C, L) tensors

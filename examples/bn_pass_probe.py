@@ -7,6 +7,9 @@ call, so it is a lower bound on what the big kernel alone reaches; small
 shapes are launch-bound.  ResNet-50 BN shapes at batch 64, bf16,
 channels_last.  "add" rows are the FusedBNAddReLU variant: its backward
 stats also write g = dy * (y > 0), and its backward apply reads g and x.
+The two "no y" columns are the backward passes of a layer without a residual
+as the modules issue them: the ReLU mask is recomputed from x, so y is not
+read (2 and 3 tensors moved instead of 3 and 4).
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,8 +45,9 @@ def timed(fn):
 
 
 print("| shape | variant | stats us (GB/s) | apply us (GB/s) | "
-      "bwd stats us (GB/s) | bwd apply us (GB/s) |")
-print("|---|---|---|---|---|---|")
+      "bwd stats us (GB/s) | bwd apply us (GB/s) | "
+      "bwd stats, no y us (GB/s) | bwd apply, no y us (GB/s) |")
+print("|---|---|---|---|---|---|---|---|")
 for shp in shapes:
     def cl():
         return torch.randn(*shp, device="cuda", dtype=dtype).contiguous(
@@ -70,9 +74,12 @@ for shp in shapes:
             ((3 if FROM_G else 4) if add else 4,
              p(3, None if (add and FROM_G) else y, dy, out)),
         )
+        if not add:
+            passes += ((2, p(4, None, dy, None)), (3, p(5, None, dy, out)))
         cells = []
         for tensors, fn in passes:
             us = timed(fn)
             cells.append(f"{us:.1f} ({tensors * nbytes / us / 1e3:.0f})")
+        cells += ["-"] * (6 - len(cells))
         print(f"| {'x'.join(map(str, shp))} | {variant} | "
               + " | ".join(cells) + " |", flush=True)

@@ -20,6 +20,11 @@ def _fusable(x):
             x.dtype in (torch.float32, torch.float16, torch.bfloat16))
 
 
+# False when HOROVOD_FUSED_BN_WORKSPACE=0 selected the earlier path for the
+# process: per-call banks with a memset, and a backward that always reads y
+_LEAN = _core.fused_bn_lean_path()
+
+
 class _FusedBNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var,
@@ -27,15 +32,26 @@ class _FusedBNReLUFn(torch.autograd.Function):
         y, mean, invstd = _core.fused_bn_relu_forward(
             x, residual, weight, bias, running_mean, running_var, momentum,
             eps)
-        ctx.save_for_backward(x, y, mean, invstd, weight)
         ctx.has_residual = residual is not None
+        # without a residual the backward recomputes the ReLU mask from x and
+        # bias, bit-equal to y > 0, so y is neither kept alive nor read
+        ctx.from_x = _LEAN and residual is None
+        if ctx.from_x:
+            ctx.save_for_backward(x, mean, invstd, weight, bias)
+        else:
+            ctx.save_for_backward(x, y, mean, invstd, weight)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, mean, invstd, weight = ctx.saved_tensors
-        outs = _core.fused_bn_relu_backward(x, y, dy, mean, invstd, weight,
-                                            ctx.has_residual)
+        if ctx.from_x:
+            x, mean, invstd, weight, bias = ctx.saved_tensors
+            outs = _core.fused_bn_relu_backward(x, None, dy, mean, invstd,
+                                                weight, False, bias)
+        else:
+            x, y, mean, invstd, weight = ctx.saved_tensors
+            outs = _core.fused_bn_relu_backward(x, y, dy, mean, invstd,
+                                                weight, ctx.has_residual)
         dx, dgamma, dbeta = outs[0], outs[1], outs[2]
         dres = outs[3] if ctx.has_residual else None
         return dx, dres, dgamma, dbeta, None, None, None, None
