@@ -288,6 +288,42 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                 invstd, gamma, beta);
         });
 
+  // ---- fused dropout + add + LayerNorm (None = absent optional tensor) -----
+  // -> [y, z|None, mean, rstd]
+  m.def("fused_ln_forward",
+        [opt_tensor](at::Tensor x, py::object residual, py::object weight,
+                     py::object bias, double p, double eps, uint64_t seed,
+                     uint64_t offset, bool save_z) {
+          return hvd::gpu::FusedLnForward(x, opt_tensor(residual),
+                                          opt_tensor(weight), opt_tensor(bias),
+                                          p, eps, seed, offset, save_z);
+        },
+        py::arg("x"), py::arg("residual"), py::arg("weight"), py::arg("bias"),
+        py::arg("p"), py::arg("eps"), py::arg("seed"), py::arg("offset"),
+        py::arg("save_z"));
+  // -> [dz, dx, dgamma|None, dbeta|None]
+  m.def("fused_ln_backward",
+        [opt_tensor](at::Tensor dy, at::Tensor z, at::Tensor mean,
+                     at::Tensor rstd, py::object weight, double p,
+                     uint64_t seed, uint64_t offset, bool need_wgrad) {
+          return hvd::gpu::FusedLnBackward(dy, z, mean, rstd,
+                                           opt_tensor(weight), p, seed, offset,
+                                           need_wgrad);
+        },
+        py::arg("dy"), py::arg("z"), py::arg("mean"), py::arg("rstd"),
+        py::arg("weight"), py::arg("p"), py::arg("seed"), py::arg("offset"),
+        py::arg("need_wgrad"));
+  // device: a torch.device or its string
+  m.def("fused_ln_keep_mask",
+        [](int64_t rows, int64_t H, double p, uint64_t seed, uint64_t offset,
+           py::object device) {
+          return hvd::gpu::FusedLnKeepMask(
+              rows, H, p, seed, offset,
+              c10::Device(py::str(device).cast<std::string>()));
+        },
+        py::arg("rows"), py::arg("H"), py::arg("p"), py::arg("seed"),
+        py::arg("offset"), py::arg("device"));
+
   // ---- SyncBatchNorm passes (None = absent optional tensor) ----------------
   m.def("sync_bn_stats",
         [](at::Tensor x) { return hvd::gpu::SyncBnStats(x); });

@@ -100,6 +100,35 @@ at::Tensor SyncBnBackwardApply(at::Tensor x, at::Tensor dy, at::Tensor mean,
                                at::Tensor invstd, at::Tensor weight,
                                at::Tensor sums, at::Tensor count);
 
+// ---- Fused dropout + residual add + LayerNorm; defined in ln.cc ------------
+// y = LayerNorm(residual + dropout(x)) over the last dimension H of a
+// contiguous x (ln_kernels.hip): H % 8 == 0, 8 <= H <= 4096, fp32 / fp16 /
+// bf16, every tensor 16-B aligned and on one GPU; residual (x's shape and
+// dtype), weight and bias (fp32 or x's dtype) may be undefined.  Anything
+// else throws before the first launch.  The dropout mask is a function of
+// (seed, offset, element index) alone, see ln_philox.h; p is quantised to
+// 1/65536.
+// -> {y, z, mean, rstd}: z = residual + dropout(x) rounded to x's dtype, only
+// with save_z and when it is not x itself (else undefined); mean / rstd fp32,
+// one per row.
+std::vector<at::Tensor> FusedLnForward(at::Tensor x, at::Tensor residual,
+                                       at::Tensor weight, at::Tensor bias,
+                                       double p, double eps, uint64_t seed,
+                                       uint64_t offset, bool save_z);
+// z: what the forward returned, or its x where that was undefined.
+// -> {dz, dx, dgamma, dbeta}: dz is the residual's gradient, dx = dz * keep *
+// scale (the same tensor as dz when p quantises to 0); dgamma / dbeta fp32
+// [H], undefined without need_wgrad.  Bitwise reproducible.
+std::vector<at::Tensor> FusedLnBackward(at::Tensor dy, at::Tensor z,
+                                        at::Tensor mean, at::Tensor rstd,
+                                        at::Tensor weight, double p,
+                                        uint64_t seed, uint64_t offset,
+                                        bool need_wgrad);
+// uint8 [rows, H], 1 where the element is kept: the mask function evaluated
+// on the host (CPU device) or in a kernel.  For tests.
+at::Tensor FusedLnKeepMask(int64_t rows, int64_t H, double p, uint64_t seed,
+                           uint64_t offset, c10::Device device);
+
 // ---- Multi-tensor kernels; defined in multi_tensor.cc ----------------------
 // Global-norm clipping (clip_kernels.hip) on torch's current stream with no
 // host synchronisation.  grads: dense fp32/fp16/bf16 tensors of one GPU, any

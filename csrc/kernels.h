@@ -5,6 +5,8 @@
 
 #include <type_traits>
 
+#include "ln_philox.h"
+
 namespace hvd {
 namespace gpu {
 
@@ -446,6 +448,43 @@ hipError_t SyncBnBwdApplyLaunch(const void* x, const void* dy, void* dx,
                                 const float* count, long long outer,
                                 long long C, long long inner, int dt,
                                 hipStream_t stream);
+
+// ---- Fused dropout + residual add + LayerNorm (ln_kernels.hip) -------------
+// Rows of H contiguous elements, [M, H]; dt in {DT_F32, DT_F16, DT_BF16} is
+// the type T of x, res, y, z, dy, dz and dx.  gamma / beta are fp32
+// (*_f32) or T, and may be null (1 and 0).  Statistics and arithmetic are
+// fp32.  H % 8 == 0, 8 <= H <= kLnMaxH and every pointer 16-B aligned, or the
+// launchers return hipErrorInvalidValue.  The dropout mask is ln_keep8
+// (ln_philox.h) of vector row * (H / 8) + col / 8.  No atomics: results are
+// bitwise reproducible.
+constexpr int kLnMaxH = 4096;
+
+// z = res + keep * scale * x (res may be null), mean / rstd its row
+// statistics (variance from the centred values), y = (z - mean) * rstd *
+// gamma + beta.  z: null, or receives z rounded to T.
+hipError_t LnForwardLaunch(const void* x, const void* res, const void* gamma,
+                           bool gamma_f32, const void* beta, bool beta_f32,
+                           void* y, void* z, float* mean, float* rstd,
+                           long long M, int H, int dt, float eps,
+                           const LnDropout& d, hipStream_t stream);
+// Partial rows LnBackwardLaunch writes for this shape.
+int LnBackwardBlocks(long long M, int H);
+// One pass over dy and z: dz = rstd * (g - mean_H(g) - xhat * mean_H(g *
+// xhat)), g = dy * gamma, xhat = (z - mean) * rstd; with d.t16 > 0 also
+// dx = dz * keep * scale (dx is not touched otherwise).  partials: null, or
+// LnBackwardBlocks rows of [2H] fp32; row b receives [sum dy * xhat (H),
+// sum dy (H)] over the rows block b visited.
+hipError_t LnBackwardLaunch(const void* dy, const void* z, const float* mean,
+                            const float* rstd, const void* gamma,
+                            bool gamma_f32, void* dz, void* dx,
+                            float* partials, long long M, int H, int dt,
+                            const LnDropout& d, hipStream_t stream);
+// out[0..2H) = the column sums of partials[rows][2H], added in a fixed order.
+hipError_t LnFoldLaunch(const float* partials, int rows, int H, float* out,
+                        hipStream_t stream);
+// out[rows][H] = 1 where the element is kept, else 0.
+hipError_t LnKeepMaskLaunch(unsigned char* out, long long rows, int H,
+                            const LnDropout& d, hipStream_t stream);
 
 }  // namespace gpu
 }  // namespace hvd
