@@ -19,6 +19,14 @@ OUT = os.path.join(ROOT, "horovod_amd", "_core.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
+# Per-file device flags.  The GELU kernels are plain scalar fp32 arithmetic
+# over 8-element vectors, which the compiler would pair into packed fp32
+# instructions; they are built without those so every element goes through
+# the same scalar instruction sequence.
+HIPFLAGS_FOR = {
+    "gelu_kernels.hip": ["-Xclang", "-target-feature",
+                         "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def torch_paths():
@@ -70,7 +78,7 @@ def build(verbose=True):
             continue
         cmd = [HIPCC, "-c", src, "-o", obj] + cxxflags
         if src.endswith(".hip"):
-            cmd += hipflags
+            cmd += hipflags + HIPFLAGS_FOR.get(os.path.basename(src), [])
         else:
             cmd += ["-x", "c++"]
         cmds.append(cmd)

@@ -324,6 +324,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows"), py::arg("H"), py::arg("p"), py::arg("seed"),
         py::arg("offset"), py::arg("device"));
 
+  // ---- fused bias + GELU + dropout (None = absent bias) --------------------
+  m.def("fused_bias_gelu_forward",
+        [opt_tensor](at::Tensor u, py::object bias, double p, uint64_t seed,
+                     uint64_t offset, bool tanh) {
+          return hvd::gpu::FusedBiasGeluForward(u, opt_tensor(bias), p, seed,
+                                                offset, tanh);
+        },
+        py::arg("u"), py::arg("bias"), py::arg("p"), py::arg("seed"),
+        py::arg("offset"), py::arg("tanh"));
+  // -> [du, dbias|None]
+  m.def("fused_bias_gelu_backward",
+        [opt_tensor](at::Tensor dy, at::Tensor u, py::object bias, double p,
+                     uint64_t seed, uint64_t offset, bool tanh,
+                     bool need_bias_grad) {
+          return hvd::gpu::FusedBiasGeluBackward(dy, u, opt_tensor(bias), p,
+                                                 seed, offset, tanh,
+                                                 need_bias_grad);
+        },
+        py::arg("dy"), py::arg("u"), py::arg("bias"), py::arg("p"),
+        py::arg("seed"), py::arg("offset"), py::arg("tanh"),
+        py::arg("need_bias_grad"));
+  m.def("fused_bias_gelu_row_chunks", &hvd::gpu::FusedBiasGeluRowChunks,
+        py::arg("M"), py::arg("N"));
+
   // ---- SyncBatchNorm passes (None = absent optional tensor) ----------------
   m.def("sync_bn_stats",
         [](at::Tensor x) { return hvd::gpu::SyncBnStats(x); });

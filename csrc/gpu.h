@@ -129,6 +129,26 @@ std::vector<at::Tensor> FusedLnBackward(at::Tensor dy, at::Tensor z,
 at::Tensor FusedLnKeepMask(int64_t rows, int64_t H, double p, uint64_t seed,
                            uint64_t offset, c10::Device device);
 
+// ---- Fused bias + GELU + dropout; defined in gelu.cc -----------------------
+// out = dropout(gelu(u + bias), p) over the last dimension N of a contiguous
+// u (gelu_kernels.hip): N % 8 == 0, N >= 8, fp32 / fp16 / bf16, every tensor
+// 16-B aligned and on one GPU; bias ([N], fp32 or u's dtype) may be
+// undefined.  tanh picks the tanh approximation over the erf form.  Anything
+// else throws before the first launch.  The mask is that of the LayerNorm
+// kernels: FusedLnKeepMask(M, N, p, seed, offset) of u viewed as [M, N].
+at::Tensor FusedBiasGeluForward(at::Tensor u, at::Tensor bias, double p,
+                                uint64_t seed, uint64_t offset, bool tanh);
+// -> {du, dbias}: du = dy * keep * scale * gelu'(u + bias) in u's dtype;
+// dbias fp32 [N], the column sums of the unrounded du, undefined without
+// need_bias_grad.  Bitwise reproducible.
+std::vector<at::Tensor> FusedBiasGeluBackward(at::Tensor dy, at::Tensor u,
+                                              at::Tensor bias, double p,
+                                              uint64_t seed, uint64_t offset,
+                                              bool tanh, bool need_bias_grad);
+// Row chunks of the launches for u of [M, N]: the partial rows the backward
+// writes (one is written straight into dbias).  For byte counts and tests.
+int64_t FusedBiasGeluRowChunks(int64_t M, int64_t N);
+
 // ---- Multi-tensor kernels; defined in multi_tensor.cc ----------------------
 // Global-norm clipping (clip_kernels.hip) on torch's current stream with no
 // host synchronisation.  grads: dense fp32/fp16/bf16 tensors of one GPU, any

@@ -485,6 +485,37 @@ hipError_t LnFoldLaunch(const float* partials, int rows, int H, float* out,
 // out[rows][H] = 1 where the element is kept, else 0.
 hipError_t LnKeepMaskLaunch(unsigned char* out, long long rows, int H,
                             const LnDropout& d, hipStream_t stream);
+// out[0..cols) = the column sums of partials[rows][cols], in the order
+// LnFoldLaunch adds them (which is this with cols = 2H).
+hipError_t ColumnFoldLaunch(const float* partials, int rows, int cols,
+                            float* out, hipStream_t stream);
+
+// ---- Fused bias + GELU + dropout (gelu_kernels.hip) ------------------------
+// out = keep * scale * gelu(u + bias) over u of [M, N] contiguous; dt as for
+// the LayerNorm kernels is the type T of u, out, dy and du.  bias is [N] fp32
+// (bias_f32) or T, or null (0).  tanh picks 0.5 v (1 + tanh(sqrt(2 / pi) (v +
+// 0.044715 v^3))) over 0.5 v (1 + erf(v / sqrt 2)).  Arithmetic is fp32 with
+// one rounding at the store.  N % 8 == 0, 8 <= N <= kGeluMaxN, M >= 1 and
+// every pointer 16-B aligned, or the launchers return hipErrorInvalidValue.
+// The dropout mask is ln_keep8 (ln_philox.h) of vector row * (N / 8) +
+// col / 8, with d.t16 == 0 an instantiation of its own.  No atomics: results
+// are bitwise reproducible.
+constexpr int kGeluMaxN = 1 << 30;
+
+// Row chunks (gridDim.y) of a launch for this shape, and the partial rows
+// GeluBackwardLaunch writes.
+int GeluRowChunks(long long M, int N);
+hipError_t GeluForwardLaunch(const void* u, const void* bias, bool bias_f32,
+                             void* out, long long M, int N, int dt, bool tanh,
+                             const LnDropout& d, hipStream_t stream);
+// du = dy * keep * scale * gelu'(u + bias) over `chunks` row chunks.
+// partials: null, or [chunks, N] fp32; row c receives the column sums of the
+// unrounded du over the rows of chunk c (zeros for an empty chunk).
+hipError_t GeluBackwardLaunch(const void* dy, const void* u, const void* bias,
+                              bool bias_f32, void* du, float* partials,
+                              int chunks, long long M, int N, int dt,
+                              bool tanh, const LnDropout& d,
+                              hipStream_t stream);
 
 }  // namespace gpu
 }  // namespace hvd

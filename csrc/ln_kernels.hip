@@ -395,13 +395,18 @@ hipError_t LnBackwardLaunch(const void* dy, const void* z, const float* mean,
   return hipGetLastError();
 }
 
-hipError_t LnFoldLaunch(const float* partials, int rows, int H, float* out,
-                        hipStream_t stream) {
-  if (rows < 1 || H < 1) return hipErrorInvalidValue;
-  const int cols = 2 * H;
+hipError_t ColumnFoldLaunch(const float* partials, int rows, int cols,
+                            float* out, hipStream_t stream) {
+  if (rows < 1 || cols < 1) return hipErrorInvalidValue;
   ln_fold_k<<<(cols + 63) / 64, kLnThreads, 0, stream>>>(partials, rows, cols,
                                                          out);
   return hipGetLastError();
+}
+
+hipError_t LnFoldLaunch(const float* partials, int rows, int H, float* out,
+                        hipStream_t stream) {
+  if (H < 1) return hipErrorInvalidValue;
+  return ColumnFoldLaunch(partials, rows, 2 * H, out, stream);
 }
 
 hipError_t LnKeepMaskLaunch(unsigned char* out, long long rows, int H,

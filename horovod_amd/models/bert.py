@@ -11,7 +11,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from horovod_amd.ops import FusedDropoutAddLayerNorm, FusedLayerNorm
+from horovod_amd.ops import (FusedDropoutAddLayerNorm, FusedLayerNorm,
+                             FusedLinearGELU)
 
 
 class BertConfig:
@@ -35,17 +36,28 @@ def _fused_ln_default():
     return os.environ.get("HOROVOD_FUSED_LN", "0") == "1"
 
 
+def _fused_gelu_default():
+    return os.environ.get("HOROVOD_FUSED_GELU", "0") == "1"
+
+
 class FusedLNEncoderLayer(nn.Module):
     """Post-LN encoder layer with the parameters of nn.TransformerEncoderLayer
     (self_attn, linear1, linear2, norm1, norm2) whose two
     LayerNorm(residual + dropout(branch)) tails are one fused kernel each
-    (horovod_amd.ops.FusedDropoutAddLayerNorm)."""
+    (horovod_amd.ops.FusedDropoutAddLayerNorm).  With fused_gelu, linear1 is
+    a FusedLinearGELU that also applies the GELU and the dropout behind
+    it."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, fused_gelu=False):
         super().__init__()
+        self.fused_gelu = fused_gelu
         self.self_attn = nn.MultiheadAttention(
             cfg.hidden, cfg.heads, dropout=cfg.dropout, batch_first=True)
-        self.linear1 = nn.Linear(cfg.hidden, cfg.intermediate)
+        if fused_gelu:
+            self.linear1 = FusedLinearGELU(cfg.hidden, cfg.intermediate,
+                                           p=cfg.dropout)
+        else:
+            self.linear1 = nn.Linear(cfg.hidden, cfg.intermediate)
         self.dropout = nn.Dropout(cfg.dropout)
         self.linear2 = nn.Linear(cfg.intermediate, cfg.hidden)
         self.norm1 = FusedDropoutAddLayerNorm(cfg.hidden, p=cfg.dropout)
@@ -74,6 +86,8 @@ class FusedLNEncoderLayer(nn.Module):
 
     def forward(self, x, key_padding_mask=None):
         h = self.norm1(self._attention(x, key_padding_mask), x)
+        if self.fused_gelu:
+            return self.norm2(self.linear2(self.linear1(h)), h)
         return self.norm2(
             self.linear2(self.dropout(F.gelu(self.linear1(h)))), h)
 
@@ -83,10 +97,10 @@ class FusedLNEncoder(nn.Module):
     nn.TransformerEncoder (layers.N.*): state_dicts load strictly both
     ways."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, fused_gelu=False):
         super().__init__()
         self.layers = nn.ModuleList(
-            FusedLNEncoderLayer(cfg) for _ in range(cfg.layers))
+            FusedLNEncoderLayer(cfg, fused_gelu) for _ in range(cfg.layers))
 
     def forward(self, src, src_key_padding_mask=None):
         for layer in self.layers:
@@ -101,14 +115,25 @@ class BertForPretraining(nn.Module):
     LayerNorms as FusedLayerNorm; None means on iff HOROVOD_FUSED_LN=1.  Off,
     the model is the stock nn.TransformerEncoder one.  Parameter names and
     shapes are the same either way.
+
+    fused_gelu: on top of fused_ln, every encoder layer's linear1 and the MLM
+    head's Linear are FusedLinearGELU (bias + GELU + dropout in one kernel
+    pass); None means on iff HOROVOD_FUSED_GELU=1.  It needs fused_ln: the
+    stock nn.TransformerEncoder has no place for the fused feed-forward.
     """
 
-    def __init__(self, cfg=BERT_LARGE, fused_ln=None):
+    def __init__(self, cfg=BERT_LARGE, fused_ln=None, fused_gelu=None):
         super().__init__()
         self.cfg = cfg
         if fused_ln is None:
             fused_ln = _fused_ln_default()
+        if fused_gelu is None:
+            fused_gelu = _fused_gelu_default()
         self.fused_ln = bool(fused_ln)
+        self.fused_gelu = bool(fused_gelu)
+        if self.fused_gelu and not self.fused_ln:
+            raise ValueError("fused_gelu needs fused_ln: the stock encoder "
+                             "has no place for the fused feed-forward")
         layer_norm = FusedLayerNorm if self.fused_ln else nn.LayerNorm
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.hidden)
         self.pos_emb = nn.Embedding(cfg.max_seq, cfg.hidden)
@@ -116,7 +141,7 @@ class BertForPretraining(nn.Module):
         self.emb_norm = layer_norm(cfg.hidden)
         self.emb_drop = nn.Dropout(cfg.dropout)
         if self.fused_ln:
-            self.encoder = FusedLNEncoder(cfg)
+            self.encoder = FusedLNEncoder(cfg, self.fused_gelu)
         else:
             layer = nn.TransformerEncoderLayer(
                 d_model=cfg.hidden, nhead=cfg.heads,
@@ -124,9 +149,15 @@ class BertForPretraining(nn.Module):
                 activation="gelu", batch_first=True, norm_first=False)
             self.encoder = nn.TransformerEncoder(layer, cfg.layers,
                                                  enable_nested_tensor=False)
-        self.mlm_transform = nn.Sequential(
-            nn.Linear(cfg.hidden, cfg.hidden), nn.GELU(),
-            layer_norm(cfg.hidden))
+        if self.fused_gelu:
+            # the same indices and key names: the GELU moves into module 0
+            self.mlm_transform = nn.Sequential(
+                FusedLinearGELU(cfg.hidden, cfg.hidden, p=0.0), nn.Identity(),
+                layer_norm(cfg.hidden))
+        else:
+            self.mlm_transform = nn.Sequential(
+                nn.Linear(cfg.hidden, cfg.hidden), nn.GELU(),
+                layer_norm(cfg.hidden))
         self.mlm_bias = nn.Parameter(torch.zeros(cfg.vocab_size))
         self.nsp = nn.Linear(cfg.hidden, 2)
 
@@ -147,9 +178,11 @@ class BertForPretraining(nn.Module):
         return mlm, nsp
 
 
-def bert_large(fused_ln=None):
-    return BertForPretraining(BERT_LARGE, fused_ln=fused_ln)
+def bert_large(fused_ln=None, fused_gelu=None):
+    return BertForPretraining(BERT_LARGE, fused_ln=fused_ln,
+                              fused_gelu=fused_gelu)
 
 
-def bert_base(fused_ln=None):
-    return BertForPretraining(BERT_BASE, fused_ln=fused_ln)
+def bert_base(fused_ln=None, fused_gelu=None):
+    return BertForPretraining(BERT_BASE, fused_ln=fused_ln,
+                              fused_gelu=fused_gelu)
