@@ -23,9 +23,12 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 # over 8-element vectors, which the compiler would pair into packed fp32
 # instructions; they are built without those so every element goes through
 # the same scalar instruction sequence.
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# bn_pool_kernels.hip is the same kind of code and is built as
+# gelu_kernels.hip is.
 HIPFLAGS_FOR = {
-    "gelu_kernels.hip": ["-Xclang", "-target-feature",
-                         "-Xclang", "-packed-fp32-ops"],
+    "gelu_kernels.hip": _NO_PACKED_FP32,
+    "bn_pool_kernels.hip": _NO_PACKED_FP32,
 }
 
 

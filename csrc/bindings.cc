@@ -277,6 +277,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("invstd"), py::arg("gamma"), py::arg("need_residual_grad"),
         py::arg("beta") = py::none());
   m.def("fused_bn_lean_path", []() { return hvd::gpu::FusedBnLeanPath(); });
+  // -> [pooled, codes, mean, invstd]
+  m.def("fused_bn_relu_pool_forward",
+        [](at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor rm,
+           at::Tensor rv, double momentum, double eps) {
+          return hvd::gpu::FusedBnReluPoolForward(x, gamma, beta, rm, rv,
+                                                  momentum, eps);
+        });
+  // -> [dx, dgamma, dbeta]
+  m.def("fused_bn_relu_pool_backward",
+        [](at::Tensor x, at::Tensor codes, at::Tensor gp, at::Tensor mean,
+           at::Tensor invstd, at::Tensor gamma, at::Tensor beta) {
+          return hvd::gpu::FusedBnReluPoolBackward(x, codes, gp, mean, invstd,
+                                                   gamma, beta);
+        });
+  m.def("fused_bn_pool_path", []() { return hvd::gpu::FusedBnPoolPath(); });
+  // -> the banks for which == 1, else None
+  m.def("fused_bn_pool_pass",
+        [](int which, at::Tensor x, at::Tensor pooled, at::Tensor codes,
+           py::object out, at::Tensor mean, at::Tensor invstd,
+           at::Tensor gamma, at::Tensor beta, py::object sum_g,
+           py::object sum_gx) -> py::object {
+          auto opt = [](const py::object& o) {
+            return o.is_none() ? at::Tensor() : o.cast<at::Tensor>();
+          };
+          at::Tensor banks = hvd::gpu::FusedBnPoolPass(
+              which, x, pooled, codes, opt(out), mean, invstd, gamma, beta,
+              opt(sum_g), opt(sum_gx));
+          if (!banks.defined()) return py::none();
+          return py::cast(banks);
+        },
+        py::arg("which"), py::arg("x"), py::arg("pooled"), py::arg("codes"),
+        py::arg("out"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
+        py::arg("beta"), py::arg("sum_g") = py::none(),
+        py::arg("sum_gx") = py::none());
   m.def("fused_bn_pass",
         [](int which, at::Tensor x, py::object a, py::object b, py::object out,
            at::Tensor mean, at::Tensor invstd, at::Tensor gamma,

@@ -1579,15 +1579,19 @@ BnBankSlot* BnSlot(int device, hipStream_t stream) {
 
 // The zeroed banks of one reduction -> consumer pair.  Normally the stream's
 // workspace; on a capturing stream, or with the switch off, a per-call
-// buffer plus memset: a capture must not allocate outside its pool, and a
-// graph must not keep a pointer to a workspace that can be dropped (below)
-// or race with eager calls on the stream it is replayed on.
+// buffer that is cleared first: a capture must not allocate outside its pool,
+// and a graph must not keep a pointer to a workspace that can be dropped
+// (below) or race with eager calls on the stream it is replayed on.
+// Eagerly the clear is a memset.  On a capturing stream the buffer comes
+// from at::zeros, whose fill ATen records as a kernel, so the graph of a
+// captured layer holds kernel nodes only (the capture status is therefore
+// asked for with the switch off too).
 class BnBankLease {
  public:
   BnBankLease(int device, hipStream_t stream, int64_t C,
               const at::TensorOptions& fopts) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (BnLeanPath()) HIP_CHECK(hipStreamIsCapturing(stream, &st));
+    HIP_CHECK(hipStreamIsCapturing(stream, &st));
     if (BnLeanPath() && st == hipStreamCaptureStatusNone) {
       slot_ = BnSlot(device, stream);
       lock_ = std::unique_lock<std::mutex>(slot_->mu);
@@ -1596,11 +1600,16 @@ class BnBankLease {
             at::zeros({(int64_t)kBnBanks * 2 * kBnMaxChannels}, fopts);
       banks_ = slot_->banks.data_ptr<float>();
     } else {
-      own_ = at::empty({(int64_t)kBnBanks * 2 * C}, fopts);
-      banks_ = own_.data_ptr<float>();
-      HIP_CHECK(hipMemsetAsync(banks_, 0,
-                               (size_t)kBnBanks * 2 * C * sizeof(float),
-                               stream));
+      if (st != hipStreamCaptureStatusNone) {
+        own_ = at::zeros({(int64_t)kBnBanks * 2 * C}, fopts);
+        banks_ = own_.data_ptr<float>();
+      } else {
+        own_ = at::empty({(int64_t)kBnBanks * 2 * C}, fopts);
+        banks_ = own_.data_ptr<float>();
+        HIP_CHECK(hipMemsetAsync(banks_, 0,
+                                 (size_t)kBnBanks * 2 * C * sizeof(float),
+                                 stream));
+      }
     }
   }
   // A launch between the reduction and its consumer failed: the banks may
@@ -1628,17 +1637,31 @@ class BnBankLease {
   bool consumed_ = false;
 };
 
-}  // namespace
+// HOROVOD_FUSED_BN_POOL=0, read once: FusedBNReLU.forward_maxpool runs the
+// BN+ReLU pass and the max-pool as two ops.
+bool BnPoolPath() {
+  static const bool on = [] {
+    const char* v = std::getenv("HOROVOD_FUSED_BN_POOL");
+    return !(v && v[0] == '0' && v[1] == '\0');
+  }();
+  return on;
+}
 
-bool FusedBnLeanPath() { return BnLeanPath(); }
+// Before anything asks x for its device: a CPU or undefined tensor gets a
+// readable message, not a failing device guard.
+void BnCheckOnGpu(const at::Tensor& x) {
+  TORCH_CHECK(x.defined() && x.is_cuda() && x.dim() == 4,
+              "fused BN expects a 4-D GPU tensor");
+}
 
-// Returns {y, save_mean, save_invstd}.  Small per-channel math ([C] tensors)
-// runs through ATen; the big passes are the CDNA4 kernels.
-std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
-                                           at::Tensor gamma, at::Tensor beta,
-                                           at::Tensor running_mean,
-                                           at::Tensor running_var,
-                                           double momentum, double eps) {
+// The training forward up to the statistics, shared by the plain and the
+// pooled forward: checks x and the parameters, reduces x, and returns
+// [mean(C), invstd(C)] after updating the running stats.  The caller holds a
+// HIPGuard for x's device and passes torch's current stream on it.
+at::Tensor BnTrainStats(const at::Tensor& x, const at::Tensor& gamma,
+                        const at::Tensor& beta, at::Tensor running_mean,
+                        at::Tensor running_var, double momentum, double eps,
+                        hipStream_t stream) {
   TORCH_CHECK(x.dim() == 4, "fused BN expects NCHW logical 4-D input");
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "fused BN requires channels_last layout");
@@ -1646,14 +1669,7 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
   TORCH_CHECK(C % 8 == 0 && C <= 4096, "fused BN requires C % 8 == 0, C <= 4096");
   TORCH_CHECK(gamma.numel() == C && beta.numel() == C,
               "fused BN: weight and bias must have C elements");
-  TORCH_CHECK(!residual.defined() ||
-                  (residual.sizes() == x.sizes() &&
-                   residual.scalar_type() == x.scalar_type() &&
-                   residual.is_contiguous(at::MemoryFormat::ChannelsLast)),
-              "fused BN: residual must match x in shape, dtype and layout");
   int device = (int)x.get_device();
-  c10::hip::HIPGuard guard(device);
-  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
   int64_t total = x.numel();
   int64_t count = total / C;
   int dt = (int)DataTypeFromTorch(x.scalar_type());
@@ -1700,14 +1716,229 @@ std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
     running_var.mul_(1 - momentum)
         .add_((var * ub).to(running_var.scalar_type()), momentum);
   }
+  return stats;
+}
+
+// The checks of a backward's inputs that do not depend on where dy comes from
+void BnCheckPoolShapes(const at::Tensor& x, const at::Tensor& pooled,
+                       const at::Tensor& codes, const char* what) {
+  const int64_t OH = (x.size(2) - 1) / 2 + 1, OW = (x.size(3) - 1) / 2 + 1;
+  TORCH_CHECK(x.size(2) >= 1 && x.size(3) >= 1 &&
+                  x.numel() / x.size(1) < (1LL << 31),
+              "fused BN pool: x needs H, W >= 1 and N * H * W < 2^31");
+  for (const at::Tensor* t : {&pooled, &codes})
+    TORCH_CHECK(t->dim() == 4 && t->size(0) == x.size(0) &&
+                    t->size(1) == x.size(1) && t->size(2) == OH &&
+                    t->size(3) == OW && t->get_device() == x.get_device() &&
+                    t->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "fused BN pool: ", what,
+                " and codes must be channels_last [N, C, (H - 1) / 2 + 1, "
+                "(W - 1) / 2 + 1] on x's device");
+  TORCH_CHECK(pooled.scalar_type() == x.scalar_type() &&
+                  codes.scalar_type() == at::kByte,
+              "fused BN pool: ", what, " has x's dtype and codes are uint8");
+}
+
+}  // namespace
+
+bool FusedBnLeanPath() { return BnLeanPath(); }
+bool FusedBnPoolPath() { return BnPoolPath(); }
+
+// Returns {y, save_mean, save_invstd}.  Small per-channel math ([C] tensors)
+// runs through ATen; the big passes are the CDNA4 kernels.
+std::vector<at::Tensor> FusedBnReluForward(at::Tensor x, at::Tensor residual,
+                                           at::Tensor gamma, at::Tensor beta,
+                                           at::Tensor running_mean,
+                                           at::Tensor running_var,
+                                           double momentum, double eps) {
+  BnCheckOnGpu(x);
+  TORCH_CHECK(!residual.defined() ||
+                  (residual.sizes() == x.sizes() &&
+                   residual.scalar_type() == x.scalar_type() &&
+                   residual.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              "fused BN: residual must match x in shape, dtype and layout");
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  at::Tensor stats = BnTrainStats(x, gamma, beta, running_mean, running_var,
+                                  momentum, eps, stream);
+  int64_t C = x.size(1);
   at::Tensor gamma_f = BnParamF32(gamma);
   at::Tensor beta_f = BnParamF32(beta);
   at::Tensor y = at::empty_like(x);
+  const float* mean_p = stats.data_ptr<float>();
   HIP_CHECK(BnApplyReluLaunch(
       x.data_ptr(), residual.defined() ? residual.data_ptr() : nullptr,
-      y.data_ptr(), mean_p, invstd_p, gamma_f.data_ptr<float>(),
-      beta_f.data_ptr<float>(), total, (int)C, dt, stream));
-  return {y, mean, invstd};
+      y.data_ptr(), mean_p, mean_p + C, gamma_f.data_ptr<float>(),
+      beta_f.data_ptr<float>(), x.numel(), (int)C,
+      (int)DataTypeFromTorch(x.scalar_type()), stream));
+  return {y, stats.narrow(0, 0, C), stats.narrow(0, C, C)};
+}
+
+// Returns {pooled, codes, save_mean, save_invstd}: the forward above followed
+// by max_pool2d(3, stride 2, padding 1), without storing the full-resolution
+// activation (bn_pool_kernels.hip).
+std::vector<at::Tensor> FusedBnReluPoolForward(at::Tensor x, at::Tensor gamma,
+                                               at::Tensor beta,
+                                               at::Tensor running_mean,
+                                               at::Tensor running_var,
+                                               double momentum, double eps) {
+  BnCheckOnGpu(x);
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  at::Tensor stats = BnTrainStats(x, gamma, beta, running_mean, running_var,
+                                  momentum, eps, stream);
+  int64_t C = x.size(1);
+  at::Tensor gamma_f = BnParamF32(gamma);
+  at::Tensor beta_f = BnParamF32(beta);
+  const int64_t OH = (x.size(2) - 1) / 2 + 1, OW = (x.size(3) - 1) / 2 + 1;
+  at::Tensor pooled = at::empty({x.size(0), C, OH, OW}, x.options(),
+                                at::MemoryFormat::ChannelsLast);
+  at::Tensor codes = at::empty({x.size(0), C, OH, OW},
+                               x.options().dtype(at::kByte),
+                               at::MemoryFormat::ChannelsLast);
+  BnCheckPoolShapes(x, pooled, codes, "pooled");
+  const float* mean_p = stats.data_ptr<float>();
+  HIP_CHECK(BnApplyReluPoolLaunch(
+      x.data_ptr(), pooled.data_ptr(), codes.data_ptr<uint8_t>(), mean_p,
+      mean_p + C, gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(),
+      x.size(0), (int)x.size(2), (int)x.size(3), (int)C,
+      (int)DataTypeFromTorch(x.scalar_type()), stream));
+  return {pooled, codes, stats.narrow(0, 0, C), stats.narrow(0, C, C)};
+}
+
+// Returns {dx, dgamma, dbeta} of the pooled forward: gp is the gradient of
+// `pooled`.  The full-resolution gradient is gathered from gp and codes inside
+// the two passes, in fp32, and the ReLU mask is recomputed from x.
+std::vector<at::Tensor> FusedBnReluPoolBackward(at::Tensor x, at::Tensor codes,
+                                                at::Tensor gp, at::Tensor mean,
+                                                at::Tensor invstd,
+                                                at::Tensor gamma,
+                                                at::Tensor beta) {
+  BnCheckOnGpu(x);
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "fused BN pool backward: x must be channels_last");
+  int64_t C = x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C <= 4096,
+              "fused BN requires C % 8 == 0, C <= 4096");
+  if (!gp.is_contiguous(at::MemoryFormat::ChannelsLast))
+    gp = gp.contiguous(at::MemoryFormat::ChannelsLast);
+  BnCheckPoolShapes(x, gp, codes, "the pooled gradient");
+  TORCH_CHECK(mean.numel() == C && invstd.numel() == C &&
+                  gamma.numel() == C && beta.numel() == C,
+              "fused BN pool backward: per-channel arrays must have C "
+              "elements");
+  int64_t count = x.numel() / C;
+  int dt = (int)DataTypeFromTorch(x.scalar_type());
+  const long long N = x.size(0);
+  const int H = (int)x.size(2), W = (int)x.size(3);
+
+  auto fopts = at::TensorOptions().dtype(at::kFloat).device(x.device());
+  at::Tensor sums = at::empty({2 * C}, fopts);
+  float* sump = sums.data_ptr<float>();
+  at::Tensor mean_f = BnParamF32(mean), invstd_f = BnParamF32(invstd);
+  at::Tensor gamma_f = BnParamF32(gamma), beta_f = BnParamF32(beta);
+  at::Tensor dx = at::empty_like(x);
+  {
+    BnBankLease lease(device, stream, C, fopts);
+    HIP_CHECK(BnBwdStatsPoolLaunch(
+        x.data_ptr(), gp.data_ptr(), codes.data_ptr<uint8_t>(),
+        mean_f.data_ptr<float>(), invstd_f.data_ptr<float>(),
+        gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(), N, H, W, (int)C,
+        dt, lease.banks(), stream));
+    HIP_CHECK(BnBankReduceLaunch(lease.banks(), sump, (int)C,
+                                 lease.persistent(), stream));
+    lease.Consumed();
+  }
+  HIP_CHECK(BnBwdApplyPoolLaunch(
+      x.data_ptr(), gp.data_ptr(), codes.data_ptr<uint8_t>(), dx.data_ptr(),
+      mean_f.data_ptr<float>(), invstd_f.data_ptr<float>(),
+      gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(), sump, sump + C, N,
+      H, W, (int)C, dt, (float)(1.0 / count), stream));
+  at::Tensor sum_g = sums.narrow(0, 0, C), sum_gx = sums.narrow(0, C, C);
+  at::Tensor dbeta = gamma.scalar_type() == at::kFloat
+                         ? sum_g
+                         : sum_g.to(gamma.scalar_type());
+  at::Tensor dgamma = gamma.scalar_type() == at::kFloat
+                          ? sum_gx
+                          : sum_gx.to(gamma.scalar_type());
+  return {dx, dgamma, dbeta};
+}
+
+// DIAGNOSTIC and test surface: one pass of the pooled path on its own, with
+// caller-supplied mean / invstd / sums (fp32 [C]).
+//   0 apply + pool (x) -> pooled, codes
+//   1 bwd stats (x, gp = pooled, codes) -> returns the kBnBanks x [2C] banks
+//   2 bwd apply (x, gp = pooled, codes, sum_g, sum_gx) -> out
+at::Tensor FusedBnPoolPass(int which, at::Tensor x, at::Tensor pooled,
+                           at::Tensor codes, at::Tensor out, at::Tensor mean,
+                           at::Tensor invstd, at::Tensor gamma,
+                           at::Tensor beta, at::Tensor sum_g,
+                           at::Tensor sum_gx) {
+  BnCheckOnGpu(x);
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "fused BN requires channels_last layout");
+  int64_t C = x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C <= 4096, "fused BN requires C % 8 == 0, C <= 4096");
+  BnCheckPoolShapes(x, pooled, codes, "pooled");
+  for (const at::Tensor* t : {&mean, &invstd, &gamma, &beta, &sum_g, &sum_gx})
+    TORCH_CHECK(!t->defined() ||
+                    (t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                     t->numel() == C && t->get_device() == x.get_device()),
+                "fused BN pool pass: per-channel arrays must be fp32 [C]");
+  TORCH_CHECK(mean.defined() && invstd.defined() && gamma.defined() &&
+                  beta.defined(),
+              "fused BN pool pass: mean, invstd, gamma and beta are needed");
+  int device = (int)x.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  int dt = (int)DataTypeFromTorch(x.scalar_type());
+  const long long N = x.size(0);
+  const int H = (int)x.size(2), W = (int)x.size(3);
+  const float* mp = mean.data_ptr<float>();
+  const float* ip = invstd.data_ptr<float>();
+  const float* gp_ = gamma.data_ptr<float>();
+  const float* bp = beta.data_ptr<float>();
+  at::Tensor banks;
+  switch (which) {
+    case 0:
+      HIP_CHECK(BnApplyReluPoolLaunch(x.data_ptr(), pooled.data_ptr(),
+                                      codes.data_ptr<uint8_t>(), mp, ip, gp_,
+                                      bp, N, H, W, (int)C, dt, stream));
+      break;
+    case 1:
+      banks = at::empty(
+          {(int64_t)kBnBanks, 2 * C},
+          at::TensorOptions().dtype(at::kFloat).device(x.device()));
+      HIP_CHECK(hipMemsetAsync(banks.data_ptr<float>(), 0,
+                               (size_t)kBnBanks * 2 * C * sizeof(float),
+                               stream));
+      HIP_CHECK(BnBwdStatsPoolLaunch(x.data_ptr(), pooled.data_ptr(),
+                                     codes.data_ptr<uint8_t>(), mp, ip, gp_,
+                                     bp, N, H, W, (int)C, dt,
+                                     banks.data_ptr<float>(), stream));
+      break;
+    case 2:
+      TORCH_CHECK(out.defined() && out.sizes() == x.sizes() &&
+                      out.scalar_type() == x.scalar_type() &&
+                      out.get_device() == x.get_device() &&
+                      out.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                      sum_g.defined() && sum_gx.defined(),
+                  "fused BN pool pass 2 needs out like x, sum_g and sum_gx");
+      HIP_CHECK(BnBwdApplyPoolLaunch(
+          x.data_ptr(), pooled.data_ptr(), codes.data_ptr<uint8_t>(),
+          out.data_ptr(), mp, ip, gp_, bp, sum_g.data_ptr<float>(),
+          sum_gx.data_ptr<float>(), N, H, W, (int)C, dt,
+          1.0f / (float)(x.numel() / C), stream));
+      break;
+    default:
+      TORCH_CHECK(false, "fused BN pool pass: which must be 0..2");
+  }
+  return banks;
 }
 
 // Returns {dx, dgamma, dbeta[, dresidual]}.  With beta given and no residual

@@ -72,6 +72,36 @@ std::vector<at::Tensor> FusedBnReluBackward(at::Tensor x, at::Tensor y,
 // False when HOROVOD_FUSED_BN_WORKSPACE=0 selected the per-call banks with
 // their memset and the y-reading backward for this process.
 bool FusedBnLeanPath();
+// The stem: BatchNorm+ReLU followed by max_pool2d(3, stride 2, padding 1) in
+// one pass that never stores the full-resolution activation
+// (bn_pool_kernels.hip).  -> {pooled, codes, save_mean, save_invstd}; codes is
+// a uint8 tensor of the pooled shape with the arg-max position 0..8 of every
+// pooled element inside its window, chosen as ATen's max-pool chooses it.
+std::vector<at::Tensor> FusedBnReluPoolForward(at::Tensor x, at::Tensor gamma,
+                                               at::Tensor beta,
+                                               at::Tensor running_mean,
+                                               at::Tensor running_var,
+                                               double momentum, double eps);
+// gp: gradient of pooled.  -> {dx, dgamma, dbeta}.  An element that is the
+// arg-max of several windows receives their fp32 sum (ATen's max-pool
+// backward rounds that sum to x's dtype first).
+std::vector<at::Tensor> FusedBnReluPoolBackward(at::Tensor x, at::Tensor codes,
+                                                at::Tensor gp, at::Tensor mean,
+                                                at::Tensor invstd,
+                                                at::Tensor gamma,
+                                                at::Tensor beta);
+// False when HOROVOD_FUSED_BN_POOL=0 turned the pooled path off for this
+// process.
+bool FusedBnPoolPath();
+// One pass of the pooled path on its own with caller-supplied statistics
+// (tests and the per-pass probe): which = 0 apply + pool -> pooled, codes;
+// 1 backward stats of (x, gp = pooled, codes), returns the kBnBanks x [2C]
+// banks; 2 backward apply of the same with sum_g / sum_gx -> out.
+at::Tensor FusedBnPoolPass(int which, at::Tensor x, at::Tensor pooled,
+                           at::Tensor codes, at::Tensor out, at::Tensor mean,
+                           at::Tensor invstd, at::Tensor gamma,
+                           at::Tensor beta, at::Tensor sum_g,
+                           at::Tensor sum_gx);
 // One big pass of the fused path on its own (per-pass timing probe):
 // which = 0 stats, 1 apply, 2 backward stats, 3 backward apply, 4 / 5 the
 // backward passes that recompute the ReLU mask from x; a / b / out may be

@@ -409,6 +409,39 @@ hipError_t BnBwdApplyLaunch(const void* x, const void* y, const void* dy,
                             long long total, int C, int dt, float inv_count,
                             hipStream_t stream);
 
+// ---- Fused BatchNorm+ReLU+MaxPool(3, 2, 1) (bn_pool_kernels.hip) -----------
+// The stem: x is NHWC dense [N, H, W, C] under the contract above, with
+// N * H * W < 2^31; pooled, gp (its gradient) and codes are NHWC dense
+// [N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C].  relu(bn(x)) at full resolution
+// is never stored.  codes (uint8) holds, per pooled element, kh * 3 + kw of
+// its arg-max in the window that starts at (2 * oh - 1, 2 * ow - 1), chosen
+// as ATen's max_pool2d chooses it (first maximum in scan order, NaN wins).
+// The launchers return hipErrorInvalidValue for a shape outside the contract
+// or a pointer that is not 16-B aligned.
+//
+// pooled = maxpool(relu(bn(x))), bit-equal to BnApplyReluLaunch followed by
+// the pool.
+hipError_t BnApplyReluPoolLaunch(const void* x, void* pooled,
+                                 unsigned char* codes, const float* mean,
+                                 const float* invstd, const float* gamma,
+                                 const float* beta, long long N, int H, int W,
+                                 int C, int dt, hipStream_t stream);
+// BnBwdStatsLaunch / BnBwdApplyLaunch with beta (mask recomputed from x),
+// where dy is gathered from gp and codes in fp32 instead of read.
+hipError_t BnBwdStatsPoolLaunch(const void* x, const void* gp,
+                                const unsigned char* codes, const float* mean,
+                                const float* invstd, const float* gamma,
+                                const float* beta, long long N, int H, int W,
+                                int C, int dt, float* banks,
+                                hipStream_t stream);
+hipError_t BnBwdApplyPoolLaunch(const void* x, const void* gp,
+                                const unsigned char* codes, void* dx,
+                                const float* mean, const float* invstd,
+                                const float* gamma, const float* beta,
+                                const float* sum_g, const float* sum_gx,
+                                long long N, int H, int W, int C, int dt,
+                                float inv_count, hipStream_t stream);
+
 // ---- SyncBatchNorm (syncbn_kernels.hip) ------------------------------------
 // Activations are a dense (outer, C, inner) block: planar (N, C, L) tensors
 // pass outer = N, inner = L; channels-last ones pass outer = N*L, inner = 1.

@@ -83,3 +83,69 @@ for shp in shapes:
         cells += ["-"] * (6 - len(cells))
         print(f"| {'x'.join(map(str, shp))} | {variant} | "
               + " | ".join(cells) + " |", flush=True)
+
+# ---- the stem: BN+ReLU followed by MaxPool2d(3, 2, 1) ------------------------
+# Two ops (apply, ATen pool forward; ATen pool backward with its zero fill,
+# backward stats and apply with the mask from x) beside the pooled passes of
+# csrc/bn_pool_kernels.hip.  MB = bytes the pass has to move, counted from the
+# shapes: the pooled passes read gp and the codes of up to 4 windows per
+# pixel, counted once (the rest comes from cache).
+if os.environ.get("BN_PROBE_STEM", "1") != "0":
+    import torch.nn.functional as F
+    shp = (64, 64, 112, 112)
+    n, c, h, w = shp
+    x = torch.randn(*shp, device="cuda", dtype=dtype).contiguous(
+        memory_format=torch.channels_last)
+    y = torch.empty_like(x)
+    out = torch.empty_like(x)
+    mean = torch.zeros(c, device="cuda")
+    invstd = torch.ones(c, device="cuda")
+    wgt = torch.ones(c, device="cuda")
+    b = torch.zeros(c, device="cuda")
+    _core.fused_bn_pass(1, x, None, None, y, mean, invstd, wgt, b)
+    pooled, idx = F.max_pool2d(y, 3, 2, 1, return_indices=True)
+    gp = torch.randn_like(pooled)
+    dy = torch.ops.aten.max_pool2d_with_indices_backward(
+        gp, y, [3, 3], [2, 2], [1, 1], [1, 1], False, idx)
+    full = x.numel() * x.element_size() / 1e6
+    small = pooled.numel() * pooled.element_size() / 1e6
+    code_mb = pooled.numel() / 1e6
+    rows = [
+        ("apply", 2 * full,
+         lambda: _core.fused_bn_pass(1, x, None, None, y, mean, invstd, wgt,
+                                     b)),
+        ("ATen pool forward", full + small + 8 * code_mb,
+         lambda: F.max_pool2d(y, 3, 2, 1, return_indices=True)),
+        ("ATen pool backward + fill", 2 * full + small + 8 * code_mb,
+         lambda: torch.ops.aten.max_pool2d_with_indices_backward(
+             gp, y, [3, 3], [2, 2], [1, 1], [1, 1], False, idx)),
+        ("bwd stats, no y", 2 * full,
+         lambda: _core.fused_bn_pass(4, x, None, dy, None, mean, invstd, wgt,
+                                     b)),
+        ("bwd apply, no y", 3 * full,
+         lambda: _core.fused_bn_pass(5, x, None, dy, out, mean, invstd, wgt,
+                                     b)),
+    ]
+    if hasattr(_core, "fused_bn_pool_pass"):
+        codes = torch.empty(pooled.shape, device="cuda",
+                            dtype=torch.uint8).contiguous(
+            memory_format=torch.channels_last)
+        p2 = torch.empty_like(pooled)
+
+        def pp(which, out_):
+            return lambda: _core.fused_bn_pool_pass(
+                which, x, p2 if which == 0 else gp, codes, out_, mean,
+                invstd, wgt, b, mean, invstd)
+        pp(0, None)()
+        rows += [
+            ("apply + pool", full + small + code_mb, pp(0, None)),
+            ("pooled bwd stats", full + small + code_mb, pp(1, None)),
+            ("pooled bwd apply", 2 * full + small + code_mb, pp(2, out)),
+        ]
+    print()
+    print(f"| stem pass, {'x'.join(map(str, shp))} | MB | us | GB/s |")
+    print("|---|---|---|---|")
+    for name, mb, fn in rows:
+        us = timed(fn)
+        print(f"| {name} | {mb:.0f} | {us:.1f} | {mb / us * 1e3:.0f} |",
+              flush=True)

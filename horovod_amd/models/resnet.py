@@ -13,6 +13,8 @@ or pass `fused_bn=False` for stock nn.BatchNorm2d + ReLU.  A `norm_layer`
 other than nn.BatchNorm2d also turns the default off.  The fused modules are
 nn.BatchNorm2d subclasses with the same parameters and state_dict keys, and
 fall back to the stock ops for CPU, eval-mode and non-channels_last inputs.
+The stem's BN+ReLU and its max-pool run as one pass
+(FusedBNReLU.forward_maxpool; HOROVOD_FUSED_BN_POOL=0 runs them as two).
 """
 import os
 
@@ -124,10 +126,12 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.bn1(self.conv1(x))
-        if not self._fused_bn:  # FusedBNReLU applies the ReLU itself
-            x = self.relu(x)
-        x = self.maxpool(x)
+        if self._fused_bn:
+            # BN, ReLU and the pool in one pass: the 64x112x112 activation
+            # between them is never stored
+            x = self.bn1.forward_maxpool(self.conv1(x), self.maxpool)
+        else:
+            x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)

@@ -3,7 +3,9 @@ csrc/bn_kernels.hip.
 
 Training-mode NHWC path: one HBM pass for normalize+affine+residual+relu
 (vs MIOpen BN + separate add + relu kernels) and one fused reduction pass in
-backward.  Eval mode, CPU tensors or non-channels-last inputs fall back to
+backward.  FusedBNReLU.forward_maxpool also takes the ResNet stem's
+MaxPool2d(3, 2, 1) into that pass (csrc/bn_pool_kernels.hip).
+Eval mode, CPU tensors or non-channels-last inputs fall back to
 the stock PyTorch ops, so the modules are drop-in (state_dict-compatible
 with nn.BatchNorm2d).
 """
@@ -57,6 +59,45 @@ class _FusedBNReLUFn(torch.autograd.Function):
         return dx, dres, dgamma, dbeta, None, None, None, None
 
 
+# False when HOROVOD_FUSED_BN_POOL=0 turned forward_maxpool's fused path off
+# for the process
+_POOL = _core.fused_bn_pool_path()
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _pool_3_2_1(pool):
+    """The one max-pool the pooled kernels cover (csrc/bn_pool_kernels.hip)."""
+    return (isinstance(pool, torch.nn.MaxPool2d) and
+            _pair(pool.kernel_size) == (3, 3) and
+            _pair(pool.stride) == (2, 2) and _pair(pool.padding) == (1, 1) and
+            _pair(pool.dilation) == (1, 1) and not pool.ceil_mode and
+            not pool.return_indices)
+
+
+class _FusedBNReLUPoolFn(torch.autograd.Function):
+    """max_pool2d(relu(bn(x)), 3, 2, 1) without the full-resolution
+    activation: the forward keeps x and one uint8 arg-max code per pooled
+    element, and the backward gathers the gradient through the codes."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
+                eps):
+        pooled, codes, mean, invstd = _core.fused_bn_relu_pool_forward(
+            x, weight, bias, running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(x, codes, mean, invstd, weight, bias)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, gp):
+        x, codes, mean, invstd, weight, bias = ctx.saved_tensors
+        dx, dgamma, dbeta = _core.fused_bn_relu_pool_backward(
+            x, codes, gp, mean, invstd, weight, bias)
+        return dx, dgamma, dbeta, None, None, None, None
+
+
 class FusedBNReLU(torch.nn.BatchNorm2d):
     """BatchNorm2d + ReLU in one kernel pass (training, NHWC)."""
 
@@ -67,6 +108,19 @@ class FusedBNReLU(torch.nn.BatchNorm2d):
                 self.weight, self.bias, self.running_mean, self.running_var,
                 self.momentum if self.momentum is not None else 0.1, self.eps)
         return F.relu(super().forward(input))
+
+    def forward_maxpool(self, input, pool):
+        """pool(self(input)) for the module's nn.MaxPool2d `pool`.  In
+        training, on an input the fused path takes and with a
+        MaxPool2d(3, stride=2, padding=1), BN, ReLU and the pool run as one
+        pass that never stores the full-resolution activation; anything else,
+        and everything under HOROVOD_FUSED_BN_POOL=0, runs the two ops."""
+        if _POOL and self.training and _fusable(input) and _pool_3_2_1(pool):
+            return _FusedBNReLUPoolFn.apply(
+                input.contiguous(memory_format=torch.channels_last),
+                self.weight, self.bias, self.running_mean, self.running_var,
+                self.momentum if self.momentum is not None else 0.1, self.eps)
+        return pool(self.forward(input))
 
 
 class FusedBNAddReLU(torch.nn.BatchNorm2d):
