@@ -382,6 +382,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_bias_gelu_row_chunks", &hvd::gpu::FusedBiasGeluRowChunks,
         py::arg("M"), py::arg("N"));
 
+  // ---- fused softmax cross-entropy -----------------------------------------
+  // -> [loss, row_loss|None, lse, count]
+  m.def("fused_xent_forward", &hvd::gpu::FusedXentForward, py::arg("logits"),
+        py::arg("labels"), py::arg("smoothing"), py::arg("ignore_index"),
+        py::arg("reduction"));
+  m.def("fused_xent_backward", &hvd::gpu::FusedXentBackward, py::arg("dloss"),
+        py::arg("logits"), py::arg("labels"), py::arg("lse"),
+        py::arg("count"), py::arg("smoothing"), py::arg("ignore_index"),
+        py::arg("reduction"));
+  m.def("fused_xent_wave_max_v", &hvd::gpu::FusedXentWaveMaxV);
+
   // ---- SyncBatchNorm passes (None = absent optional tensor) ----------------
   m.def("sync_bn_stats",
         [](at::Tensor x) { return hvd::gpu::SyncBnStats(x); });

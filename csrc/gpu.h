@@ -179,6 +179,31 @@ std::vector<at::Tensor> FusedBiasGeluBackward(at::Tensor dy, at::Tensor u,
 // writes (one is written straight into dbias).  For byte counts and tests.
 int64_t FusedBiasGeluRowChunks(int64_t M, int64_t N);
 
+// ---- Fused softmax cross-entropy; defined in xent.cc -----------------------
+// F.cross_entropy of contiguous [M, V] fp32 / fp16 / bf16 logits against
+// contiguous int64 labels [M] on the same GPU (xent_kernels.hip), with label
+// smoothing 0 <= smoothing < 1 and reduction "none", "mean" or "sum".  The
+// logits' base pointer is 16-B aligned; V is arbitrary.  Anything else throws
+// before the first launch.  A label equal to ignore_index gives loss 0 and a
+// zero gradient row; one that is neither that nor in [0, V) gives NaN for
+// both and is never used as an index.
+// -> {loss, row_loss, lse, count}, all fp32: loss is [M] for "none" (row_loss
+// is then undefined) and 0-dim otherwise, row_loss and lse are [M], count is
+// the 0-dim number of labels that are not ignore_index.  Bitwise reproducible.
+std::vector<at::Tensor> FusedXentForward(at::Tensor logits, at::Tensor labels,
+                                         double smoothing,
+                                         int64_t ignore_index,
+                                         const std::string& reduction);
+// dloss: fp32, [M] for "none", else one element; lse and count as the forward
+// returned them.  -> dx in the logits' dtype, rounded once.
+at::Tensor FusedXentBackward(at::Tensor dloss, at::Tensor logits,
+                             at::Tensor labels, at::Tensor lse,
+                             at::Tensor count, double smoothing,
+                             int64_t ignore_index,
+                             const std::string& reduction);
+// Longest row that is given one wave; a longer one gets a block.
+int64_t FusedXentWaveMaxV();
+
 // ---- Multi-tensor kernels; defined in multi_tensor.cc ----------------------
 // Global-norm clipping (clip_kernels.hip) on torch's current stream with no
 // host synchronisation.  grads: dense fp32/fp16/bf16 tensors of one GPU, any

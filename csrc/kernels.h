@@ -550,5 +550,49 @@ hipError_t GeluBackwardLaunch(const void* dy, const void* u, const void* bias,
                               bool tanh, const LnDropout& d,
                               hipStream_t stream);
 
+// ---- Fused softmax cross-entropy (xent_kernels.hip) ------------------------
+// Rows of V contiguous logits, [M, V]; dt in {DT_F32, DT_F16, DT_BF16} is the
+// type T of x and dx, labels are int64, every statistic and all arithmetic is
+// fp32.  Only the base pointers of x and dx have to be 16-B aligned: V is
+// arbitrary, so a row starts at any multiple of sizeof(T), and the kernels
+// peel each row to its own 16-B boundary.  1 <= V <= kXentMaxV, 1 <= M <=
+// kXentMaxM and 0 <= eps < 1, or the launchers return hipErrorInvalidValue.
+// No atomics: results are bitwise reproducible.
+//
+// Rows of up to kXentWaveMaxV elements are given one wave each, four rows per
+// block; longer rows one 256-thread block each.  At 2048 bf16 elements a lane
+// of the wave has exactly the four 16-B loads in flight that the kernels
+// unroll to; past that a lone wave would loop where a block's four waves
+// still work side by side.
+constexpr int kXentWaveMaxV = 2048;
+constexpr int kXentMaxV = 1 << 30;
+constexpr long long kXentMaxM = 2147483647LL;
+
+// lse[r] = log sum_c exp(x[r, c]); row_loss[r] = lse[r] - (1 - eps) x[r, y_r]
+// - (eps / V) sum_c x[r, c], which is F.cross_entropy's label_smoothing; 0
+// where y_r == ignore_index, NaN where y_r is neither that nor in [0, V) (such
+// a label is never used as an index).
+hipError_t XentForwardLaunch(const void* x, const long long* labels,
+                             float* lse, float* row_loss, long long M, int V,
+                             int dt, float eps, long long ignore_index,
+                             hipStream_t stream);
+// out[0] = the row losses added in a fixed order, divided with `mean` by
+// out[1] = the number of labels that are not ignore_index (0 / 0 = NaN).
+hipError_t XentFoldLaunch(const float* row_loss, const long long* labels,
+                          long long M, long long ignore_index, bool mean,
+                          float* out, hipStream_t stream);
+// Column chunks (gridDim.y) the backward cuts the rows of this shape into.
+int XentBackwardChunks(long long M, int V, int dt);
+// dx[r, c] = g_r (exp(x[r, c] - lse[r]) - (1 - eps) [c == y_r] - eps / V),
+// rounded once to T.  reduction 0 (none): g_r = dloss[r]; 1 (mean): dloss[0]
+// / count[0]; 2 (sum): dloss[0]; all read on the device.  A row with y_r ==
+// ignore_index is written as zeros without reading x; one with a label that
+// is neither that nor in [0, V) as NaN.
+hipError_t XentBackwardLaunch(const void* x, const long long* labels,
+                              const float* lse, const float* dloss,
+                              const float* count, void* dx, long long M, int V,
+                              int dt, float eps, long long ignore_index,
+                              int reduction, hipStream_t stream);
+
 }  // namespace gpu
 }  // namespace hvd

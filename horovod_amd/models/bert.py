@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from horovod_amd.ops import (FusedDropoutAddLayerNorm, FusedLayerNorm,
-                             FusedLinearGELU)
+                             FusedLinearGELU, softmax_cross_entropy)
 
 
 class BertConfig:
@@ -38,6 +38,10 @@ def _fused_ln_default():
 
 def _fused_gelu_default():
     return os.environ.get("HOROVOD_FUSED_GELU", "0") == "1"
+
+
+def _fused_xent_default():
+    return os.environ.get("HOROVOD_FUSED_XENT", "0") == "1"
 
 
 class FusedLNEncoderLayer(nn.Module):
@@ -176,6 +180,35 @@ class BertForPretraining(nn.Module):
         mlm = self.mlm_transform(h) @ self.tok_emb.weight.t() + self.mlm_bias
         nsp = self.nsp(h[:, 0])
         return mlm, nsp
+
+
+class BertPretrainingLoss(nn.Module):
+    """The pretraining loss of BertForPretraining's two outputs: the MLM
+    cross-entropy over mlm_logits.flatten(0, 1), where a label of -100 marks a
+    position that was not masked, plus the NSP cross-entropy.
+
+    fused: take the MLM term through horovod_amd.ops.softmax_cross_entropy,
+    which reads the [B * S, V] logits in their own dtype instead of an fp32
+    copy; None means on iff HOROVOD_FUSED_XENT=1, read when the module is
+    built.  Off, the module is the two F.cross_entropy calls.  The NSP term is
+    F.cross_entropy either way: its logits are [B, 2], a few hundred bytes,
+    and two launches of the fused kernels would buy nothing there.
+    """
+
+    def __init__(self, fused=None):
+        super().__init__()
+        if fused is None:
+            fused = _fused_xent_default()
+        self.fused = bool(fused)
+
+    def forward(self, mlm_logits, nsp_logits, mlm_labels, nsp_labels):
+        mlm_ce = softmax_cross_entropy if self.fused else F.cross_entropy
+        return (mlm_ce(mlm_logits.flatten(0, 1), mlm_labels.flatten(),
+                       ignore_index=-100) +
+                F.cross_entropy(nsp_logits, nsp_labels))
+
+    def extra_repr(self):
+        return f"fused={self.fused}"
 
 
 def bert_large(fused_ln=None, fused_gelu=None):
