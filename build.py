@@ -24,13 +24,14 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 # instructions; they are built without those so every element goes through
 # the same scalar instruction sequence.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# bn_pool_kernels.hip and xent_kernels.hip (the same fp32 step over the 4 or 8
-# elements of a 16-byte vector) are the same kind of code and are built as
-# gelu_kernels.hip is.
+# bn_pool_kernels.hip, xent_kernels.hip and xent_bias_kernels.hip (the same
+# fp32 step over the 4 or 8 elements of a 16-byte vector) are the same kind of
+# code and are built as gelu_kernels.hip is.
 HIPFLAGS_FOR = {
     "gelu_kernels.hip": _NO_PACKED_FP32,
     "bn_pool_kernels.hip": _NO_PACKED_FP32,
     "xent_kernels.hip": _NO_PACKED_FP32,
+    "xent_bias_kernels.hip": _NO_PACKED_FP32,
 }
 
 

@@ -392,6 +392,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("count"), py::arg("smoothing"), py::arg("ignore_index"),
         py::arg("reduction"));
   m.def("fused_xent_wave_max_v", &hvd::gpu::FusedXentWaveMaxV);
+  // the loss of logits + bias; -> [loss, row_loss|None, lse, count]
+  m.def("fused_xent_bias_forward", &hvd::gpu::FusedXentBiasForward,
+        py::arg("logits"), py::arg("bias"), py::arg("labels"),
+        py::arg("smoothing"), py::arg("ignore_index"), py::arg("reduction"));
+  // -> [dx, dbias]
+  m.def("fused_xent_bias_backward", &hvd::gpu::FusedXentBiasBackward,
+        py::arg("dloss"), py::arg("logits"), py::arg("bias"),
+        py::arg("labels"), py::arg("lse"), py::arg("count"),
+        py::arg("smoothing"), py::arg("ignore_index"), py::arg("reduction"));
+  m.def("fused_xent_bias_row_chunks", &hvd::gpu::FusedXentBiasRowChunks,
+        py::arg("M"), py::arg("V"), py::arg("dtype"));
 
   // ---- SyncBatchNorm passes (None = absent optional tensor) ----------------
   m.def("sync_bn_stats",

@@ -203,6 +203,29 @@ at::Tensor FusedXentBackward(at::Tensor dloss, at::Tensor logits,
                              const std::string& reduction);
 // Longest row that is given one wave; a longer one gets a block.
 int64_t FusedXentWaveMaxV();
+// The same loss of logits + bias, bias a contiguous fp32 [V] tensor on the
+// logits' GPU, added in fp32 inside the kernels (xent_bias_kernels.hip): the
+// sum is never stored.  -> {loss, row_loss, lse, count} as above, with lse =
+// 0 for a row whose label is ignore_index (such a row is not read).
+std::vector<at::Tensor> FusedXentBiasForward(at::Tensor logits,
+                                             at::Tensor bias,
+                                             at::Tensor labels,
+                                             double smoothing,
+                                             int64_t ignore_index,
+                                             const std::string& reduction);
+// -> {dx, dbias}: dx in the logits' dtype, rounded once; dbias fp32 [V], the
+// column sums of the unrounded dx.  Bitwise reproducible.
+std::vector<at::Tensor> FusedXentBiasBackward(at::Tensor dloss,
+                                              at::Tensor logits,
+                                              at::Tensor bias,
+                                              at::Tensor labels,
+                                              at::Tensor lse, at::Tensor count,
+                                              double smoothing,
+                                              int64_t ignore_index,
+                                              const std::string& reduction);
+// Row chunks of each phase class in the backward for [M, V] logits of this
+// dtype.  For byte counts and tests.
+int64_t FusedXentBiasRowChunks(int64_t M, int64_t V, at::ScalarType dtype);
 
 // ---- Multi-tensor kernels; defined in multi_tensor.cc ----------------------
 // Global-norm clipping (clip_kernels.hip) on torch's current stream with no

@@ -594,5 +594,39 @@ hipError_t XentBackwardLaunch(const void* x, const long long* labels,
                               int dt, float eps, long long ignore_index,
                               int reduction, hipStream_t stream);
 
+// ---- The same with a bias folded in (xent_bias_kernels.hip) ----------------
+// z = x + bias in fp32, bias fp32 [V], takes the place of x in every formula
+// above; x, dx, labels, the limits and the reductions are as above, and bias
+// has no alignment to keep.  The rows r, r + P, r + 2P, ... start at one
+// offset from a 16-B boundary, so they share one cut into head, body vectors
+// and tail: they form phase class r mod P.
+// P = 16 / gcd(16, (V * sizeof(T)) mod 16): 1, 2, 4 or 8 (at most 4 for fp32).
+int XentBiasPhases(int V, int dt);
+// Floats between the P shifted copies of the bias the forward reads.
+inline long long XentBiasPitch(int V) { return ((long long)V + 3) / 4 * 4; }
+// shift: P * XentBiasPitch(V) floats, 16-B aligned, written here by a small
+// kernel ahead of the row kernel: copy p holds bias from the first body
+// column of class p on, so that a body vector's bias is read in 16-B loads.
+// A row with y_r == ignore_index is not read: row_loss[r] = lse[r] = 0.
+hipError_t XentBiasForwardLaunch(const void* x, const float* bias,
+                                 const long long* labels, float* shift,
+                                 float* lse, float* row_loss, long long M,
+                                 int V, int dt, float eps,
+                                 long long ignore_index, hipStream_t stream);
+// Row chunks of each phase class in the backward, which writes P * chunks
+// partial rows.
+int XentBiasRowChunks(long long M, int V, int dt);
+// dx as XentBackwardLaunch with z for x.  partials: [P * chunks, V] fp32, chunks
+// = XentBiasRowChunks; row p * chunks + c receives, for every column, the sum
+// of the unrounded dx over the rows of chunk c of class p in rising row order
+// (zeros for an empty chunk).  Their column sums are dbias.
+hipError_t XentBiasBackwardLaunch(const void* x, const float* bias,
+                                  const long long* labels, const float* lse,
+                                  const float* dloss, const float* count,
+                                  void* dx, float* partials, long long M,
+                                  int V, int dt, float eps,
+                                  long long ignore_index, int reduction,
+                                  hipStream_t stream);
+
 }  // namespace gpu
 }  // namespace hvd

@@ -127,5 +127,104 @@ at::Tensor FusedXentBackward(at::Tensor dloss, at::Tensor logits,
 
 int64_t FusedXentWaveMaxV() { return kXentWaveMaxV; }
 
+// ---- with the bias folded in (xent_bias_kernels.hip) ------------------------
+// Next to the outputs the forward allocates the shifted copies of the bias its
+// kernel reads, and the backward the partial rows of the bias gradient.
+
+namespace {
+
+void CheckBias(const at::Tensor& bias, const at::Tensor& logits, int64_t V) {
+  if (!bias.defined() || !bias.is_cuda() ||
+      bias.get_device() != logits.get_device() ||
+      bias.scalar_type() != at::kFloat || bias.dim() != 1 ||
+      bias.size(0) != V || !bias.is_contiguous())
+    XentFail("needs bias as " + std::to_string(V) +
+             " contiguous fp32 elements, [V], on the logits' GPU");
+}
+
+}  // namespace
+
+std::vector<at::Tensor> FusedXentBiasForward(at::Tensor logits,
+                                             at::Tensor bias,
+                                             at::Tensor labels,
+                                             double smoothing,
+                                             int64_t ignore_index,
+                                             const std::string& reduction) {
+  const XentShape s = CheckInputs(logits, labels, smoothing, reduction);
+  CheckBias(bias, logits, s.V);
+  const int device = (int)logits.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  auto fopts = at::TensorOptions().dtype(at::kFloat).device(logits.device());
+  at::Tensor lse = at::empty({s.M}, fopts);
+  at::Tensor row_loss = at::empty({s.M}, fopts);
+  at::Tensor folded = at::empty({2}, fopts);  // {loss, count}
+  at::Tensor shift = at::empty(
+      {XentBiasPhases((int)s.V, s.dt), XentBiasPitch((int)s.V)}, fopts);
+  if (((uintptr_t)shift.data_ptr() % 16) != 0)
+    XentFail("needs 16-byte aligned data (shifted bias)");
+  const long long* y = (const long long*)labels.data_ptr();
+  HIP_CHECK(XentBiasForwardLaunch(
+      logits.data_ptr(), bias.data_ptr<float>(), y, shift.data_ptr<float>(),
+      lse.data_ptr<float>(), row_loss.data_ptr<float>(), s.M, (int)s.V, s.dt,
+      (float)smoothing, ignore_index, stream));
+  HIP_CHECK(XentFoldLaunch(row_loss.data_ptr<float>(), y, s.M, ignore_index,
+                           s.reduction == 1, folded.data_ptr<float>(),
+                           stream));
+  at::Tensor count = folded.select(0, 1);
+  if (s.reduction == 0) return {row_loss, at::Tensor(), lse, count};
+  return {folded.select(0, 0), row_loss, lse, count};
+}
+
+std::vector<at::Tensor> FusedXentBiasBackward(at::Tensor dloss,
+                                              at::Tensor logits,
+                                              at::Tensor bias,
+                                              at::Tensor labels,
+                                              at::Tensor lse, at::Tensor count,
+                                              double smoothing,
+                                              int64_t ignore_index,
+                                              const std::string& reduction) {
+  const XentShape s = CheckInputs(logits, labels, smoothing, reduction);
+  CheckBias(bias, logits, s.V);
+  CheckF32(dloss, logits, s.reduction == 0 ? s.M : 1, "dloss");
+  CheckF32(lse, logits, s.M, "lse");
+  CheckF32(count, logits, 1, "count");
+  const int device = (int)logits.get_device();
+  c10::hip::HIPGuard guard(device);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(device).stream();
+  at::Tensor dx = at::empty_like(logits);
+  if (((uintptr_t)dx.data_ptr() % 16) != 0)
+    XentFail("needs 16-byte aligned data (dx)");
+  auto fopts = at::TensorOptions().dtype(at::kFloat).device(logits.device());
+  const int64_t rows = (int64_t)XentBiasPhases((int)s.V, s.dt) *
+                       XentBiasRowChunks(s.M, (int)s.V, s.dt);
+  at::Tensor dbias = at::empty({s.V}, fopts);
+  // a single partial row is the gradient itself
+  at::Tensor partials = rows == 1 ? dbias : at::empty({rows, s.V}, fopts);
+  HIP_CHECK(XentBiasBackwardLaunch(
+      logits.data_ptr(), bias.data_ptr<float>(),
+      (const long long*)labels.data_ptr(), lse.data_ptr<float>(),
+      dloss.data_ptr<float>(), count.data_ptr<float>(), dx.data_ptr(),
+      partials.data_ptr<float>(), s.M, (int)s.V, s.dt, (float)smoothing,
+      ignore_index, s.reduction, stream));
+  if (rows > 1)
+    HIP_CHECK(ColumnFoldLaunch(partials.data_ptr<float>(), (int)rows, (int)s.V,
+                               dbias.data_ptr<float>(), stream));
+  return {dx, dbias};
+}
+
+int64_t FusedXentBiasRowChunks(int64_t M, int64_t V, at::ScalarType dtype) {
+  if (M < 1 || V < 1 || V > kXentMaxV || M > kXentMaxM)
+    XentFail("row chunks need 1 <= M <= 2^31 - 1 and 1 <= V <= 2^30");
+  int dt;
+  switch (dtype) {
+    case at::kFloat: dt = DT_F32; break;
+    case at::kHalf: dt = DT_F16; break;
+    case at::kBFloat16: dt = DT_BF16; break;
+    default: XentFail("supports fp32, fp16 and bf16 logits only");
+  }
+  return XentBiasRowChunks(M, (int)V, dt);
+}
+
 }  // namespace gpu
 }  // namespace hvd

@@ -19,8 +19,18 @@ above what the logits and labels hold.  bytes / time is an end-to-end rate of
 the call (launches and allocator included), not a kernel's share of peak;
 kernel times come from a kernel trace of this script, one path per process
 (XENT_SHAPES=8192x30522 XENT_PATHS=fused).
+
+--bias times the loss of logits + bias instead, bias an fp32 [V] parameter as
+BERT's mlm_bias is, both paths through softmax_cross_entropy:
+  added   softmax_cross_entropy(x + b, y): ATen adds (reads 2 E, writes 4 E),
+          the kernels read fp32 (4 E forward, 4 E + 4 E backward), autograd
+          casts the gradient down (6 E) and sums it over rows (4 E): 28 E
+  folded  softmax_cross_entropy(x, y, bias=b): 6 E as above, plus the partial
+          rows of the bias gradient, written once and read once
+Every label is valid here too, so the folded forward skips no row.
 Needs a GPU: a measurement without one would say nothing.
 """
+import math
 import os
 import sys
 
@@ -28,10 +38,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
+from horovod_amd import _core  # noqa: E402
 from horovod_amd.ops import softmax_cross_entropy  # noqa: E402
 
+BIAS = "--bias" in sys.argv[1:]
 SHAPES = [(1024, 30522), (8192, 30522)]
-PATHS = ["fused", "stock"]
+PATHS = ["added", "folded"] if BIAS else ["fused", "stock"]
 if os.environ.get("XENT_SHAPES"):
     SHAPES = [tuple(int(v) for v in sh.split("x"))
               for sh in os.environ["XENT_SHAPES"].split(",")]
@@ -40,22 +52,30 @@ if os.environ.get("XENT_PATHS"):
 WINDOW = float(os.environ.get("XENT_WINDOW", "0.5"))
 REPEATS = int(os.environ.get("XENT_REPEATS", "3"))
 WARMUP = 5
-FNS = {"fused": softmax_cross_entropy, "stock": F.cross_entropy}
+FNS = {"fused": lambda x, y, b: softmax_cross_entropy(x, y),
+       "stock": lambda x, y, b: F.cross_entropy(x, y),
+       "added": lambda x, y, b: softmax_cross_entropy(x + b, y),
+       "folded": lambda x, y, b: softmax_cross_entropy(x, y, bias=b)}
 
 
 def path_bytes(M, V):
     E = M * V
-    return {"fused": 6 * E + 8 * M + 12 * M, "stock": 36 * E + 8 * M}
+    # partial rows of the bias gradient: phase classes x row chunks
+    rows = (16 // math.gcd(16, V * 2 % 16) *
+            _core.fused_xent_bias_row_chunks(M, V, torch.bfloat16))
+    return {"fused": 6 * E + 8 * M + 12 * M, "stock": 36 * E + 8 * M,
+            "added": 28 * E + 8 * M + 12 * M,
+            "folded": 6 * E + 8 * M + 12 * M + 8 * rows * V}
 
 
-def step(fn, x, y):
+def step(fn, x, y, b):
     with torch.autocast("cuda", torch.bfloat16):
-        loss = fn(x, y)
+        loss = fn(x, y, b)
     loss.backward()
-    x.grad = None
+    x.grad = b.grad = None
 
 
-def window(names, x, y, rounds):
+def window(names, x, y, b, rounds):
     """ms per forward + backward of each path over `rounds` alternating
     rounds, from device events around every call"""
     marks = []
@@ -63,7 +83,7 @@ def window(names, x, y, rounds):
         for n in names:
             e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
             e0.record()
-            step(FNS[n], x, y)
+            step(FNS[n], x, y, b)
             e1.record()
             marks.append((n, e0, e1))
     torch.cuda.synchronize()
@@ -71,11 +91,11 @@ def window(names, x, y, rounds):
             for n in names}
 
 
-def peak_bytes(fn, x, y):
+def peak_bytes(fn, x, y, b):
     torch.cuda.synchronize()
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
-    step(fn, x, y)
+    step(fn, x, y, b)
     torch.cuda.synchronize()
     return torch.cuda.max_memory_allocated() - base
 
@@ -84,7 +104,8 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("xent_microbench needs a GPU")
     names = [n for n in FNS if n in PATHS]
-    print(f"bf16 logits under bf16 autocast, forward + backward; {REPEATS} "
+    print(f"bf16 logits{' + fp32 bias' if BIAS else ''} under bf16 autocast, "
+          f"forward + backward; {REPEATS} "
           f"windows of at least {WINDOW} s after {WARMUP} warm-up rounds")
     print(f"{'shape':>12} {'path':>6} {'MB moved':>9} {'ms':>8} {'min':>8} "
           f"{'max':>8} {'GB/s':>8} {'peak MB':>9}")
@@ -93,18 +114,19 @@ def main():
         x = torch.randn(M, V, device="cuda", generator=g).bfloat16()
         x.requires_grad_(True)
         y = torch.randint(0, V, (M,), device="cuda", generator=g)
+        b = torch.randn(V, device="cuda", generator=g).requires_grad_(True)
         for _ in range(WARMUP):
-            window(names, x, y, 1)
-        per_round = sum(window(names, x, y, 5).values()) / 1e3
+            window(names, x, y, b, 1)
+        per_round = sum(window(names, x, y, b, 5).values()) / 1e3
         rounds = max(10, int(WINDOW / per_round) + 1)
-        runs = [window(names, x, y, rounds) for _ in range(REPEATS)]
+        runs = [window(names, x, y, b, rounds) for _ in range(REPEATS)]
         nbytes = path_bytes(M, V)
         for n in names:
             ts = [r[n] for r in runs]
             t = sum(ts) / len(ts)
             print(f"{M:>6}x{V:<5} {n:>6} {nbytes[n] / 1e6:9.1f} {t:8.4f} "
                   f"{min(ts):8.4f} {max(ts):8.4f} {nbytes[n] / t / 1e6:8.1f} "
-                  f"{peak_bytes(FNS[n], x, y) / 1e6:9.1f}")
+                  f"{peak_bytes(FNS[n], x, y, b) / 1e6:9.1f}")
 
 
 if __name__ == "__main__":

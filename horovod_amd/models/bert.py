@@ -165,7 +165,11 @@ class BertForPretraining(nn.Module):
         self.mlm_bias = nn.Parameter(torch.zeros(cfg.vocab_size))
         self.nsp = nn.Linear(cfg.hidden, 2)
 
-    def forward(self, input_ids, token_type_ids=None, attention_mask=None):
+    def forward(self, input_ids, token_type_ids=None, attention_mask=None,
+                add_mlm_bias=True):
+        """add_mlm_bias=False returns the MLM logits as the vocabulary GEMM
+        leaves them (bf16 under autocast), for a loss that adds mlm_bias
+        itself: BertPretrainingLoss(fused=True)(..., mlm_bias=model.mlm_bias)."""
         b, s = input_ids.shape
         pos = torch.arange(s, device=input_ids.device).unsqueeze(0)
         x = self.tok_emb(input_ids) + self.pos_emb(pos)
@@ -177,7 +181,9 @@ class BertForPretraining(nn.Module):
             pad_mask = attention_mask == 0
         h = self.encoder(x, src_key_padding_mask=pad_mask)
         # tied MLM head (weight sharing with tok_emb, BERT-standard)
-        mlm = self.mlm_transform(h) @ self.tok_emb.weight.t() + self.mlm_bias
+        mlm = self.mlm_transform(h) @ self.tok_emb.weight.t()
+        if add_mlm_bias:
+            mlm = mlm + self.mlm_bias
         nsp = self.nsp(h[:, 0])
         return mlm, nsp
 
@@ -193,6 +199,10 @@ class BertPretrainingLoss(nn.Module):
     built.  Off, the module is the two F.cross_entropy calls.  The NSP term is
     F.cross_entropy either way: its logits are [B, 2], a few hundred bytes,
     and two launches of the fused kernels would buy nothing there.
+
+    mlm_bias: the model's mlm_bias when mlm_logits come from
+    model(..., add_mlm_bias=False).  With fused the kernels add it as they read
+    the logits and return its gradient; without, it is added here.
     """
 
     def __init__(self, fused=None):
@@ -201,11 +211,17 @@ class BertPretrainingLoss(nn.Module):
             fused = _fused_xent_default()
         self.fused = bool(fused)
 
-    def forward(self, mlm_logits, nsp_logits, mlm_labels, nsp_labels):
-        mlm_ce = softmax_cross_entropy if self.fused else F.cross_entropy
-        return (mlm_ce(mlm_logits.flatten(0, 1), mlm_labels.flatten(),
-                       ignore_index=-100) +
-                F.cross_entropy(nsp_logits, nsp_labels))
+    def forward(self, mlm_logits, nsp_logits, mlm_labels, nsp_labels,
+                mlm_bias=None):
+        mlm_logits, mlm_labels = mlm_logits.flatten(0, 1), mlm_labels.flatten()
+        if self.fused:
+            mlm = softmax_cross_entropy(mlm_logits, mlm_labels,
+                                        ignore_index=-100, bias=mlm_bias)
+        else:
+            if mlm_bias is not None:
+                mlm_logits = mlm_logits + mlm_bias
+            mlm = F.cross_entropy(mlm_logits, mlm_labels, ignore_index=-100)
+        return mlm + F.cross_entropy(nsp_logits, nsp_labels)
 
     def extra_repr(self):
         return f"fused={self.fused}"

@@ -17,6 +17,16 @@ bf16 GPU tensor with at least one element and the labels a contiguous int64
 class-probability targets, other label dtypes) is
 F.cross_entropy(logits.float(), labels, ...).  There are no class weights.
 
+bias: a [V] tensor added to every row of the logits inside the kernels
+(csrc/xent_bias_kernels.hip), in fp32, so that the loss is that of logits +
+bias without the sum ever being stored: under autocast a bf16 GEMM output
+plus an fp32 bias parameter is an fp32 [M, V] tensor, and so is its gradient.
+The backward returns the bias gradient next to the logits' (fp32 column sums
+of the unrounded gradient, cast only for a bias that is not fp32).  Native
+when the logits and labels are as above and the bias is a contiguous [V]
+floating-point tensor on the same device; everything else is
+F.cross_entropy(logits.float() + bias.float(), labels, ...).
+
 Labels: ignore_index rows have loss 0 and a zero gradient row, and do not
 count in the mean; with every row ignored 'mean' is NaN, as in torch.  A label
 that is neither ignore_index nor in [0, V) makes that row's loss and gradient
@@ -66,6 +76,37 @@ class _FusedXentFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
+def _bias_eligible(logits, bias):
+    return (torch.is_tensor(bias) and bias.device == logits.device and
+            bias.is_floating_point() and bias.shape == logits.shape[1:] and
+            bias.is_contiguous())
+
+
+class _FusedXentBiasFn(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, logits, bias, labels, smoothing, ignore_index,
+                reduction):
+        ctx.bias_dtype = bias.dtype
+        bias = bias.detach().float()
+        loss, _, lse, count = _core.fused_xent_bias_forward(
+            logits, bias, labels, smoothing, ignore_index, reduction)
+        ctx.args = (smoothing, ignore_index, reduction)
+        ctx.save_for_backward(logits, bias, labels, lse, count)
+        return loss
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dloss):
+        logits, bias, labels, lse, count = ctx.saved_tensors
+        dloss = dloss.float().contiguous()
+        if dloss.data_ptr() % 16 != 0:
+            dloss = dloss.clone()
+        dx, dbias = _core.fused_xent_bias_backward(
+            dloss, logits, bias, labels, lse, count, *ctx.args)
+        return dx, dbias.to(ctx.bias_dtype), None, None, None, None
+
+
 def _check(label_smoothing, reduction):
     if not 0.0 <= label_smoothing < 1.0:
         raise ValueError("label_smoothing has to be in [0, 1), but got "
@@ -77,10 +118,21 @@ def _check(label_smoothing, reduction):
 
 
 def softmax_cross_entropy(logits, labels, label_smoothing=0.0,
-                          ignore_index=-100, reduction="mean"):
+                          ignore_index=-100, reduction="mean", bias=None):
     """F.cross_entropy(logits, labels, ...) without class weights, as an fp32
-    loss for every logits dtype."""
+    loss for every logits dtype; with a bias [V], the loss of logits +
+    bias."""
     label_smoothing, reduction = _check(label_smoothing, reduction)
+    if bias is not None:
+        if _eligible(logits, labels) and _bias_eligible(logits, bias):
+            return _FusedXentBiasFn.apply(logits, bias, labels,
+                                          label_smoothing, int(ignore_index),
+                                          reduction)
+        # F.cross_entropy keeps the classes in dimension 1
+        bias = bias.float().view(-1, *[1] * max(logits.dim() - 2, 0))
+        return F.cross_entropy(logits.float() + bias, labels,
+                               ignore_index=ignore_index, reduction=reduction,
+                               label_smoothing=label_smoothing)
     if _eligible(logits, labels):
         return _FusedXentFn.apply(logits, labels, label_smoothing,
                                   int(ignore_index), reduction)
@@ -99,9 +151,9 @@ class FusedCrossEntropyLoss(nn.Module):
                                                       reduction)
         self.ignore_index = ignore_index
 
-    def forward(self, input, target):
+    def forward(self, input, target, bias=None):
         return softmax_cross_entropy(input, target, self.label_smoothing,
-                                     self.ignore_index, self.reduction)
+                                     self.ignore_index, self.reduction, bias)
 
     def extra_repr(self):
         return (f"label_smoothing={self.label_smoothing}, "
