@@ -382,6 +382,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_bias_gelu_row_chunks", &hvd::gpu::FusedBiasGeluRowChunks,
         py::arg("M"), py::arg("N"));
 
+  // ---- fused self-attention (None = no key padding mask) -------------------
+  // -> [out, lse]
+  m.def("fused_attention_forward",
+        [opt_tensor](at::Tensor qkv, py::object key_padding_mask,
+                     int64_t heads, double p, uint64_t seed, uint64_t offset) {
+          return hvd::gpu::FusedAttentionForward(
+              qkv, opt_tensor(key_padding_mask), heads, p, seed, offset);
+        },
+        py::arg("qkv"), py::arg("key_padding_mask"), py::arg("heads"),
+        py::arg("p"), py::arg("seed"), py::arg("offset"));
+  // -> dqkv
+  m.def("fused_attention_backward",
+        [opt_tensor](at::Tensor dout, at::Tensor qkv, at::Tensor out,
+                     at::Tensor lse, py::object key_padding_mask,
+                     int64_t heads, double p, uint64_t seed, uint64_t offset) {
+          return hvd::gpu::FusedAttentionBackward(
+              dout, qkv, out, lse, opt_tensor(key_padding_mask), heads, p,
+              seed, offset);
+        },
+        py::arg("dout"), py::arg("qkv"), py::arg("out"), py::arg("lse"),
+        py::arg("key_padding_mask"), py::arg("heads"), py::arg("p"),
+        py::arg("seed"), py::arg("offset"));
+
   // ---- fused softmax cross-entropy -----------------------------------------
   // -> [loss, row_loss|None, lse, count]
   m.def("fused_xent_forward", &hvd::gpu::FusedXentForward, py::arg("logits"),

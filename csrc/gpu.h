@@ -179,6 +179,25 @@ std::vector<at::Tensor> FusedBiasGeluBackward(at::Tensor dy, at::Tensor u,
 // writes (one is written straight into dbias).  For byte counts and tests.
 int64_t FusedBiasGeluRowChunks(int64_t M, int64_t N);
 
+// ---- Fused multi-head self-attention; defined in attn.cc -------------------
+// Softmax attention with dropout on the packed in_proj output qkv [B, S, 3E]
+// (attn_kernels.hip; kernels.h has the definition and the mask indexing): E =
+// 64 * heads, 1 <= S <= 512, fp16 / bf16, contiguous and 16-B aligned.
+// key_padding_mask: undefined, or a contiguous bool [B, S] on qkv's GPU, true
+// = padding.  Anything else throws before the first launch.
+// -> {out [B, S, E] in qkv's dtype, lse [B, heads, S] fp32}.  A sequence whose
+// keys are all padding gets out = 0 and lse = -inf (and zero gradients), where
+// the stock softmax gives NaN.
+std::vector<at::Tensor> FusedAttentionForward(at::Tensor qkv,
+                                              at::Tensor key_padding_mask,
+                                              int64_t heads, double p,
+                                              uint64_t seed, uint64_t offset);
+// -> dqkv [B, S, 3E], every element written once.  Bitwise reproducible.
+at::Tensor FusedAttentionBackward(at::Tensor dout, at::Tensor qkv,
+                                  at::Tensor out, at::Tensor lse,
+                                  at::Tensor key_padding_mask, int64_t heads,
+                                  double p, uint64_t seed, uint64_t offset);
+
 // ---- Fused softmax cross-entropy; defined in xent.cc -----------------------
 // F.cross_entropy of contiguous [M, V] fp32 / fp16 / bf16 logits against
 // contiguous int64 labels [M] on the same GPU (xent_kernels.hip), with label

@@ -628,5 +628,34 @@ hipError_t XentBiasBackwardLaunch(const void* x, const float* bias,
                                   long long ignore_index, int reduction,
                                   hipStream_t stream);
 
+// ---- Fused multi-head self-attention (attn_kernels.hip) --------------------
+// qkv is the packed in_proj output [B, S, 3E], E = 64 H: q | k | v, head h in
+// columns 64h .. 64h + 63 of each; dt in {DT_F16, DT_BF16} is the type T of
+// qkv, out, dout and dqkv.  mask: null, or [B, S] bytes, nonzero = padding
+// key.  s_ij = 0.125 q_i . k_j, p = softmax over the allowed keys, a = keep *
+// scale * p, o = a v.  The dropout mask is ln_keep8 (ln_philox.h) over the
+// matrix [B * H * S, S8], S8 = S rounded up to a multiple of 8: element (b,
+// h, i, j) is bit j % 8 of vector ((b * H + h) * S + i) * (S8 / 8) + j / 8.
+// Statistics and accumulators are fp32; P and dS are rounded to T once, as
+// operands of the second product.  1 <= S <= kAttnMaxS, B, H in [1, 65535],
+// qkv, out, dout and dqkv 16-B aligned, or the launchers return
+// hipErrorInvalidValue.  No atomics: results are bitwise reproducible.
+constexpr int kAttnMaxS = 512;
+constexpr int kAttnHeadDim = 64;
+
+// out [B, S, E]; lse [B, H, S] = log sum_j exp(s_ij) over the allowed keys.
+// A query with no allowed key gets out = 0 and lse = -inf.
+hipError_t AttnForwardLaunch(const void* qkv, const unsigned char* mask,
+                             void* out, float* lse, long long B, int S, int H,
+                             int dt, const LnDropout& d, hipStream_t stream);
+// dqkv [B, S, 3E], every element written once, by two kernels: the first
+// writes dq and D [B, H, S] (D_i = do_i . o_i, a workspace), the second reads
+// D and writes dk and dv.  P is recomputed from lse.
+hipError_t AttnBackwardLaunch(const void* dout, const void* qkv,
+                              const void* out, const float* lse,
+                              const unsigned char* mask, void* dqkv, float* D,
+                              long long B, int S, int H, int dt,
+                              const LnDropout& d, hipStream_t stream);
+
 }  // namespace gpu
 }  // namespace hvd

@@ -12,7 +12,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from horovod_amd.ops import (FusedDropoutAddLayerNorm, FusedLayerNorm,
-                             FusedLinearGELU, softmax_cross_entropy)
+                             FusedLinearGELU, self_attention,
+                             softmax_cross_entropy)
 
 
 class BertConfig:
@@ -40,6 +41,10 @@ def _fused_gelu_default():
     return os.environ.get("HOROVOD_FUSED_GELU", "0") == "1"
 
 
+def _fused_attn_default():
+    return os.environ.get("HOROVOD_FUSED_ATTN", "0") == "1"
+
+
 def _fused_xent_default():
     return os.environ.get("HOROVOD_FUSED_XENT", "0") == "1"
 
@@ -50,11 +55,14 @@ class FusedLNEncoderLayer(nn.Module):
     LayerNorm(residual + dropout(branch)) tails are one fused kernel each
     (horovod_amd.ops.FusedDropoutAddLayerNorm).  With fused_gelu, linear1 is
     a FusedLinearGELU that also applies the GELU and the dropout behind
-    it."""
+    it.  With fused_attn, the attention core between in_proj and out_proj is
+    horovod_amd.ops.self_attention on the packed in_proj output; self_attn
+    still holds the parameters."""
 
-    def __init__(self, cfg, fused_gelu=False):
+    def __init__(self, cfg, fused_gelu=False, fused_attn=False):
         super().__init__()
         self.fused_gelu = fused_gelu
+        self.fused_attn = fused_attn
         self.self_attn = nn.MultiheadAttention(
             cfg.hidden, cfg.heads, dropout=cfg.dropout, batch_first=True)
         if fused_gelu:
@@ -77,6 +85,12 @@ class FusedLNEncoderLayer(nn.Module):
         attn = self.self_attn
         b, s, e = x.shape
         qkv = F.linear(x, attn.in_proj_weight, attn.in_proj_bias)
+        if self.fused_attn:
+            mask = key_padding_mask
+            if mask is not None and mask.dtype != torch.bool:
+                mask = mask.bool()
+            return attn.out_proj(self_attention(
+                qkv, attn.num_heads, mask, attn.dropout, self.training))
         q, k, v = (t.view(b, s, attn.num_heads, attn.head_dim).transpose(1, 2)
                    for t in qkv.chunk(3, dim=-1))
         mask = None
@@ -101,10 +115,11 @@ class FusedLNEncoder(nn.Module):
     nn.TransformerEncoder (layers.N.*): state_dicts load strictly both
     ways."""
 
-    def __init__(self, cfg, fused_gelu=False):
+    def __init__(self, cfg, fused_gelu=False, fused_attn=False):
         super().__init__()
         self.layers = nn.ModuleList(
-            FusedLNEncoderLayer(cfg, fused_gelu) for _ in range(cfg.layers))
+            FusedLNEncoderLayer(cfg, fused_gelu, fused_attn)
+            for _ in range(cfg.layers))
 
     def forward(self, src, src_key_padding_mask=None):
         for layer in self.layers:
@@ -124,20 +139,33 @@ class BertForPretraining(nn.Module):
     head's Linear are FusedLinearGELU (bias + GELU + dropout in one kernel
     pass); None means on iff HOROVOD_FUSED_GELU=1.  It needs fused_ln: the
     stock nn.TransformerEncoder has no place for the fused feed-forward.
+
+    fused_attn: on top of fused_ln, every encoder layer's attention core runs
+    on the project's matrix-instruction kernels
+    (horovod_amd.ops.self_attention); None means on iff HOROVOD_FUSED_ATTN=1.
+    It needs fused_ln for the same reason.  A sequence whose keys are all
+    padding then gets zeros from the attention, not NaN.
     """
 
-    def __init__(self, cfg=BERT_LARGE, fused_ln=None, fused_gelu=None):
+    def __init__(self, cfg=BERT_LARGE, fused_ln=None, fused_gelu=None,
+                 fused_attn=None):
         super().__init__()
         self.cfg = cfg
         if fused_ln is None:
             fused_ln = _fused_ln_default()
         if fused_gelu is None:
             fused_gelu = _fused_gelu_default()
+        if fused_attn is None:
+            fused_attn = _fused_attn_default()
         self.fused_ln = bool(fused_ln)
         self.fused_gelu = bool(fused_gelu)
+        self.fused_attn = bool(fused_attn)
         if self.fused_gelu and not self.fused_ln:
             raise ValueError("fused_gelu needs fused_ln: the stock encoder "
                              "has no place for the fused feed-forward")
+        if self.fused_attn and not self.fused_ln:
+            raise ValueError("fused_attn needs fused_ln: the stock encoder "
+                             "has no place for the fused attention")
         layer_norm = FusedLayerNorm if self.fused_ln else nn.LayerNorm
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.hidden)
         self.pos_emb = nn.Embedding(cfg.max_seq, cfg.hidden)
@@ -145,7 +173,8 @@ class BertForPretraining(nn.Module):
         self.emb_norm = layer_norm(cfg.hidden)
         self.emb_drop = nn.Dropout(cfg.dropout)
         if self.fused_ln:
-            self.encoder = FusedLNEncoder(cfg, self.fused_gelu)
+            self.encoder = FusedLNEncoder(cfg, self.fused_gelu,
+                                          self.fused_attn)
         else:
             layer = nn.TransformerEncoderLayer(
                 d_model=cfg.hidden, nhead=cfg.heads,
@@ -227,11 +256,11 @@ class BertPretrainingLoss(nn.Module):
         return f"fused={self.fused}"
 
 
-def bert_large(fused_ln=None, fused_gelu=None):
+def bert_large(fused_ln=None, fused_gelu=None, fused_attn=None):
     return BertForPretraining(BERT_LARGE, fused_ln=fused_ln,
-                              fused_gelu=fused_gelu)
+                              fused_gelu=fused_gelu, fused_attn=fused_attn)
 
 
-def bert_base(fused_ln=None, fused_gelu=None):
+def bert_base(fused_ln=None, fused_gelu=None, fused_attn=None):
     return BertForPretraining(BERT_BASE, fused_ln=fused_ln,
-                              fused_gelu=fused_gelu)
+                              fused_gelu=fused_gelu, fused_attn=fused_attn)
