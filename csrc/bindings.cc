@@ -358,6 +358,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows"), py::arg("H"), py::arg("p"), py::arg("seed"),
         py::arg("offset"), py::arg("device"));
 
+  // ---- fused embedding + LayerNorm + dropout (None = absent tensor) --------
+  // -> [y, mean, rstd]
+  m.def("fused_emb_forward",
+        [opt_tensor](at::Tensor ids, py::object types, at::Tensor tok,
+                     at::Tensor pos, py::object typ, py::object weight,
+                     py::object bias, double p, double eps, uint64_t seed,
+                     uint64_t offset, at::ScalarType out_dtype) {
+          return hvd::gpu::FusedEmbForward(
+              ids, opt_tensor(types), tok, pos, opt_tensor(typ),
+              opt_tensor(weight), opt_tensor(bias), p, eps, seed, offset,
+              out_dtype);
+        },
+        py::arg("input_ids"), py::arg("token_type_ids"), py::arg("tok_weight"),
+        py::arg("pos_weight"), py::arg("type_weight"), py::arg("ln_weight"),
+        py::arg("ln_bias"), py::arg("p"), py::arg("eps"), py::arg("seed"),
+        py::arg("offset"), py::arg("out_dtype"));
+  // -> [dtok, dpos, dtype|None, dgamma, dbeta]
+  m.def("fused_emb_backward",
+        [opt_tensor](at::Tensor dy, at::Tensor ids, py::object types,
+                     at::Tensor tok, at::Tensor pos, py::object typ,
+                     py::object weight, at::Tensor mean, at::Tensor rstd,
+                     double p, uint64_t seed, uint64_t offset) {
+          return hvd::gpu::FusedEmbBackward(
+              dy, ids, opt_tensor(types), tok, pos, opt_tensor(typ),
+              opt_tensor(weight), mean, rstd, p, seed, offset);
+        },
+        py::arg("dy"), py::arg("input_ids"), py::arg("token_type_ids"),
+        py::arg("tok_weight"), py::arg("pos_weight"), py::arg("type_weight"),
+        py::arg("ln_weight"), py::arg("mean"), py::arg("rstd"), py::arg("p"),
+        py::arg("seed"), py::arg("offset"));
+
   // ---- fused bias + GELU + dropout (None = absent bias) --------------------
   m.def("fused_bias_gelu_forward",
         [opt_tensor](at::Tensor u, py::object bias, double p, uint64_t seed,

@@ -159,6 +159,32 @@ std::vector<at::Tensor> FusedLnBackward(at::Tensor dy, at::Tensor z,
 at::Tensor FusedLnKeepMask(int64_t rows, int64_t H, double p, uint64_t seed,
                            uint64_t offset, c10::Device device);
 
+// ---- Fused embedding + LayerNorm + dropout; defined in emb.cc --------------
+// y[b, s] = dropout(LayerNorm(tok[ids[b, s]] + pos[s] (+ typ[types[b, s]])), p)
+// in out_dtype (emb_kernels.hip): ids / types contiguous int64 [B, S] on one
+// GPU (types and typ may be undefined together), tables [rows, H] and weight /
+// bias [H] (either may be undefined) contiguous, 16-B aligned and fp32 or
+// out_dtype, H % 8 == 0 and 8 <= H <= 4096, S at most pos's rows, typ of at
+// most 2 rows.  Anything else throws before the first launch.  The mask is
+// FusedLnKeepMask(B * S, H, p, seed, offset).  An id outside its table makes
+// its row NaN and adds nothing to any gradient.
+// -> {y [B, S, H], mean, rstd}: mean / rstd fp32, one per row.
+std::vector<at::Tensor> FusedEmbForward(at::Tensor ids, at::Tensor types,
+                                        at::Tensor tok, at::Tensor pos,
+                                        at::Tensor typ, at::Tensor weight,
+                                        at::Tensor bias, double p, double eps,
+                                        uint64_t seed, uint64_t offset,
+                                        at::ScalarType out_dtype);
+// dy in the forward's out_dtype.  -> {dtok, dpos, dtyp, dgamma, dbeta}, all
+// fp32 and of the parameters' shapes, every element written once; dtyp is
+// undefined without types.  Bitwise reproducible.
+std::vector<at::Tensor> FusedEmbBackward(at::Tensor dy, at::Tensor ids,
+                                         at::Tensor types, at::Tensor tok,
+                                         at::Tensor pos, at::Tensor typ,
+                                         at::Tensor weight, at::Tensor mean,
+                                         at::Tensor rstd, double p,
+                                         uint64_t seed, uint64_t offset);
+
 // ---- Fused bias + GELU + dropout; defined in gelu.cc -----------------------
 // out = dropout(gelu(u + bias), p) over the last dimension N of a contiguous
 // u (gelu_kernels.hip): N % 8 == 0, N >= 8, fp32 / fp16 / bf16, every tensor

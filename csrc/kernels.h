@@ -657,5 +657,60 @@ hipError_t AttnBackwardLaunch(const void* dout, const void* qkv,
                               long long B, int S, int H, int dt,
                               const LnDropout& d, hipStream_t stream);
 
+// ---- Fused embedding + LayerNorm + dropout (emb_kernels.hip) ---------------
+// Row r = b * S + s of ids [B, S]: z = tok[ids_r] + pos[s] (+ typ[types_r]),
+// y = keep * scale * (gamma * (z - mean) * rstd + beta), statistics over H in
+// fp32.  dt is the type T of y and dy; every table and parameter is fp32
+// (its *_f32 flag) or T.  H % 8 == 0, 8 <= H <= kLnMaxH, S <= P, at most
+// kEmbMaxTypes type rows and every pointer 16-B aligned, or the launchers
+// return hipErrorInvalidValue.  The dropout mask is ln_keep8 (ln_philox.h) of
+// vector r * (H / 8) + col / 8.  An id outside [0, V) or a type outside
+// [0, ntypes) is clamped before it is used as an index; its row of y is NaN
+// and adds nothing to any gradient.  No atomics: results are bitwise
+// reproducible.
+constexpr int kEmbMaxTypes = 2;
+
+struct EmbTables {
+  const long long* ids = nullptr;    // [B, S]
+  const long long* types = nullptr;  // [B, S], or null: no type row is added
+  const void* tok = nullptr;         // [V, H]
+  const void* pos = nullptr;         // [P, H]
+  const void* typ = nullptr;         // [ntypes, H]; unused without types
+  const void* gamma = nullptr;       // [H], or null (1)
+  const void* beta = nullptr;        // [H], or null (0); forward only
+  bool tok_f32 = true, pos_f32 = true, typ_f32 = true;
+  bool gamma_f32 = true, beta_f32 = true;
+  int B = 0, S = 0, H = 0, P = 0, ntypes = 0;
+  long long V = 0;
+};
+
+// Batch chunks (gridDim.y) of the forward or the backward launch for this
+// shape, and the blocks along positions (gridDim.x); the backward writes one
+// partial row per block.
+int EmbBatchChunks(int B, int S, int H, bool backward);
+int EmbPositionBlocks(int S, int H);
+// y [B * S, H] of T, mean / rstd [B * S] fp32.
+hipError_t EmbForwardLaunch(const EmbTables& t, void* y, float* mean,
+                            float* rstd, int dt, float eps,
+                            const LnDropout& d, hipStream_t stream);
+// Pass one of the backward: dz [B * S, H] fp32, the gradient of z (zeros for
+// a row with a bad index).  dpos_part [chunks, S, H] fp32: row c receives the
+// sums of dz over the batch entries of chunk c.  wpart [blocks, nacc * H]
+// fp32, blocks = EmbPositionBlocks * chunks and nacc = 4 with types, else 2:
+// [sum dy keep scale xhat, sum dy keep scale, sum dz of type 0, of type 1]
+// over the rows the block visited.
+hipError_t EmbBackwardLaunch(const EmbTables& t, const void* dy,
+                             const float* mean, const float* rstd, float* dz,
+                             float* dpos_part, float* wpart, int chunks,
+                             int dt, const LnDropout& d, hipStream_t stream);
+// Pass two: dtok [V, H] fp32, row v = the sum of the rows perm[j] of dz over
+// the segment of sorted_ids [M] that equals v, in rising j (zeros for an
+// empty segment), and rows [S, P) of dpos [P, H] = 0.  sorted_ids / perm are
+// the stable sort of ids and its permutation.
+hipError_t EmbScatterLaunch(const long long* sorted_ids,
+                            const long long* perm, const float* dz,
+                            float* dtok, float* dpos, long long M, int H,
+                            long long V, int S, int P, hipStream_t stream);
+
 }  // namespace gpu
 }  // namespace hvd

@@ -12,8 +12,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from horovod_amd.ops import (FusedDropoutAddLayerNorm, FusedLayerNorm,
-                             FusedLinearGELU, self_attention,
-                             softmax_cross_entropy)
+                             FusedLinearGELU, embedding_layer_norm,
+                             self_attention, softmax_cross_entropy)
 
 
 class BertConfig:
@@ -43,6 +43,10 @@ def _fused_gelu_default():
 
 def _fused_attn_default():
     return os.environ.get("HOROVOD_FUSED_ATTN", "0") == "1"
+
+
+def _fused_emb_default():
+    return os.environ.get("HOROVOD_FUSED_EMB", "0") == "1"
 
 
 def _fused_xent_default():
@@ -145,10 +149,16 @@ class BertForPretraining(nn.Module):
     (horovod_amd.ops.self_attention); None means on iff HOROVOD_FUSED_ATTN=1.
     It needs fused_ln for the same reason.  A sequence whose keys are all
     padding then gets zeros from the attention, not NaN.
+
+    fused_emb: on top of fused_ln, the three embedding lookups, emb_norm and
+    emb_drop run as one kernel pass (horovod_amd.ops.embedding_layer_norm) on
+    the parameters of those modules, and hand the encoder its activations in
+    the autocast dtype; None means on iff HOROVOD_FUSED_EMB=1.  It needs
+    fused_ln for the same reason.
     """
 
     def __init__(self, cfg=BERT_LARGE, fused_ln=None, fused_gelu=None,
-                 fused_attn=None):
+                 fused_attn=None, fused_emb=None):
         super().__init__()
         self.cfg = cfg
         if fused_ln is None:
@@ -157,9 +167,15 @@ class BertForPretraining(nn.Module):
             fused_gelu = _fused_gelu_default()
         if fused_attn is None:
             fused_attn = _fused_attn_default()
+        if fused_emb is None:
+            fused_emb = _fused_emb_default()
         self.fused_ln = bool(fused_ln)
         self.fused_gelu = bool(fused_gelu)
         self.fused_attn = bool(fused_attn)
+        self.fused_emb = bool(fused_emb)
+        if self.fused_emb and not self.fused_ln:
+            raise ValueError("fused_emb needs fused_ln: it hands the encoder "
+                             "activations in the autocast dtype")
         if self.fused_gelu and not self.fused_ln:
             raise ValueError("fused_gelu needs fused_ln: the stock encoder "
                              "has no place for the fused feed-forward")
@@ -199,12 +215,19 @@ class BertForPretraining(nn.Module):
         """add_mlm_bias=False returns the MLM logits as the vocabulary GEMM
         leaves them (bf16 under autocast), for a loss that adds mlm_bias
         itself: BertPretrainingLoss(fused=True)(..., mlm_bias=model.mlm_bias)."""
-        b, s = input_ids.shape
-        pos = torch.arange(s, device=input_ids.device).unsqueeze(0)
-        x = self.tok_emb(input_ids) + self.pos_emb(pos)
-        if token_type_ids is not None:
-            x = x + self.type_emb(token_type_ids)
-        x = self.emb_drop(self.emb_norm(x))
+        if self.fused_emb:
+            x = embedding_layer_norm(
+                input_ids, token_type_ids, self.tok_emb.weight,
+                self.pos_emb.weight, self.type_emb.weight,
+                self.emb_norm.weight, self.emb_norm.bias, self.emb_drop.p,
+                self.emb_norm.eps, self.training)
+        else:
+            b, s = input_ids.shape
+            pos = torch.arange(s, device=input_ids.device).unsqueeze(0)
+            x = self.tok_emb(input_ids) + self.pos_emb(pos)
+            if token_type_ids is not None:
+                x = x + self.type_emb(token_type_ids)
+            x = self.emb_drop(self.emb_norm(x))
         pad_mask = None
         if attention_mask is not None:
             pad_mask = attention_mask == 0
@@ -256,11 +279,15 @@ class BertPretrainingLoss(nn.Module):
         return f"fused={self.fused}"
 
 
-def bert_large(fused_ln=None, fused_gelu=None, fused_attn=None):
+def bert_large(fused_ln=None, fused_gelu=None, fused_attn=None,
+               fused_emb=None):
     return BertForPretraining(BERT_LARGE, fused_ln=fused_ln,
-                              fused_gelu=fused_gelu, fused_attn=fused_attn)
+                              fused_gelu=fused_gelu, fused_attn=fused_attn,
+                              fused_emb=fused_emb)
 
 
-def bert_base(fused_ln=None, fused_gelu=None, fused_attn=None):
+def bert_base(fused_ln=None, fused_gelu=None, fused_attn=None,
+              fused_emb=None):
     return BertForPretraining(BERT_BASE, fused_ln=fused_ln,
-                              fused_gelu=fused_gelu, fused_attn=fused_attn)
+                              fused_gelu=fused_gelu, fused_attn=fused_attn,
+                              fused_emb=fused_emb)
