@@ -46,6 +46,15 @@ __device__ __forceinline__ __hip_bfloat16 from_d<__hip_bfloat16>(double v) {
   return (__hip_bfloat16)(float)v;
 }
 
+// ac*a + bc*b with each product rounded on its own.  A fused multiply-add
+// keeps one product unrounded, so with b = -a (ac == bc) the sum would be
+// the other product's rounding error instead of zero.
+__device__ __forceinline__ double scaled_add(double ac, double a, double bc,
+                                             double b) {
+#pragma clang fp contract(off)
+  return ac * a + bc * b;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void adasum_dots_k(AdasumBatchArgs args,
                                                      double* dots) {
@@ -133,12 +142,12 @@ __global__ __launch_bounds__(256) void adasum_scaledadd_k(AdasumBatchArgs args,
       vb.u = ((const uint4*)b)[i];
 #pragma unroll
       for (int k = 0; k < VS; ++k)
-        va.e[k] = from_d<T>(ac * to_d<T>(va.e[k]) + bc * to_d<T>(vb.e[k]));
+        va.e[k] = from_d<T>(scaled_add(ac, to_d<T>(va.e[k]), bc, to_d<T>(vb.e[k])));
       ((uint4*)a)[i] = va.u;
     }
   }
   for (long long i = done + tid; i < n; i += nthreads) {
-    a[i] = from_d<T>(ac * to_d<T>(a[i]) + bc * to_d<T>(b[i]));
+    a[i] = from_d<T>(scaled_add(ac, to_d<T>(a[i]), bc, to_d<T>(b[i])));
   }
 }
 

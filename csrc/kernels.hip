@@ -47,14 +47,19 @@ __device__ __forceinline__ DstT convert_scale(SrcT v, AccT scale) {
   return (DstT)((AccT)v * scale);
 }
 
-// no-scale specializations preserve integer exactness
-template <typename T>
-__device__ __forceinline__ T convert_only(T v) {
-  return v;
-}
+// no-scale path: a same-type copy returns the value untouched (a bit copy for
+// every type, 64-bit integers and fp64 included), an integer pair converts
+// as integers, and only a float-family pair goes through fp32
 template <typename SrcT, typename DstT>
 __device__ __forceinline__ DstT convert_only(SrcT v) {
-  return (DstT)(float)v;
+  if constexpr (std::is_same<SrcT, DstT>::value) {
+    return v;
+  } else if constexpr (std::is_integral<SrcT>::value &&
+                       std::is_integral<DstT>::value) {
+    return (DstT)v;
+  } else {
+    return (DstT)(float)v;
+  }
 }
 
 template <typename SrcT, typename DstT, bool WITH_SCALE>
@@ -184,6 +189,12 @@ hipError_t BatchedCopyLaunch(const CopyBatchArgs& args, int src_dt, int dst_dt,
     }
     return hipErrorInvalidValue;
   }
+  // int16 tensors travel as int32: RCCL has no 16-bit integer type, and an
+  // int32 reduction truncated on unpack equals the wrapping int16 one
+  if (!with_scale && src_dt == DT_I16 && dst_dt == DT_I32)
+    return launch_pair<short, int>(args, false, blocks_per_copy, stream);
+  if (!with_scale && src_dt == DT_I32 && dst_dt == DT_I16)
+    return launch_pair<int, short>(args, false, blocks_per_copy, stream);
   // float-family conversions (+ optional scale)
   switch (src_dt) {
     case DT_F32:

@@ -78,6 +78,19 @@ def _dtype_code(dtype):
         raise ValueError(f"horovod_amd: unsupported dtype {dtype}")
 
 
+def _wire_code(tensor, wire_dtype):
+    """Wire DataType code of one allreduce.  Without compression it is the
+    tensor's own dtype, except for int16 GPU tensors: RCCL has no 16-bit
+    integer type, so the pack kernel widens them to int32 and the unpack
+    kernel truncates the reduced values back (equal to a wrapping int16
+    reduction)."""
+    if wire_dtype is not None:
+        return _dtype_code(wire_dtype)
+    if tensor.dtype == torch.int16 and tensor.is_cuda:
+        return _dtype_code(torch.int32)
+    return _dtype_code(tensor.dtype)
+
+
 def _dense_ok(t):
     """True when the tensor occupies a dense (non-overlapping) block of
     memory, possibly with permuted strides (e.g. channels_last).  Dense
@@ -228,8 +241,7 @@ def _do_allreduce_async(tensor, output, average, name, op, prescale_factor,
         post = 1.0
     ps_id = _set_id(process_set)
     name = name or _next_name("allreduce")
-    wire_code = (_dtype_code(wire_dtype) if wire_dtype is not None
-                 else _dtype_code(tensor.dtype))
+    wire_code = _wire_code(tensor, wire_dtype)
     return _allreduce_async_impl([tensor], [output], ["allreduce." + name],
                                  true_op, pre, post, ps_id, wire_code,
                                  post_divisor=post_div)
@@ -338,8 +350,7 @@ def _grouped_allreduce_impl(tensors, outputs, average, name, op,
     ps_id = _set_id(process_set)
     base = name or _next_name("grouped_allreduce")
     names = [f"allreduce.{base}.{i}" for i in range(len(tensors))]
-    wire_code = (_dtype_code(wire_dtype) if wire_dtype is not None
-                 else _dtype_code(tensors[0].dtype))
+    wire_code = _wire_code(tensors[0], wire_dtype)
     return _allreduce_async_impl(list(tensors), list(outputs), names, true_op,
                                  pre, post, ps_id, wire_code, kind="grouped",
                                  post_divisor=post_div)

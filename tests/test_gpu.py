@@ -73,6 +73,8 @@ def test_allreduce_dtypes_gpu(hvd):
     for dtype in [torch.float32, torch.float16, torch.bfloat16, torch.int32,
                   torch.int64, torch.uint8]:
         t = (torch.arange(100, device="cuda") % 17).to(dtype)
+        if dtype in (torch.int32, torch.int64):
+            t[7] = 2**24 + 1  # not representable in fp32
         out = hvd.allreduce(t, average=False, name=f"gdt{dtype}")
         assert torch.equal(out, t), dtype
 
