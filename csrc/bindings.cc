@@ -389,6 +389,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ln_weight"), py::arg("mean"), py::arg("rstd"), py::arg("p"),
         py::arg("seed"), py::arg("offset"));
 
+  // ---- compaction of the labelled rows -------------------------------------
+  // -> [idx, rank, row_labels, count]
+  m.def("masked_rows_index", &hvd::gpu::MaskedRowsIndex, py::arg("labels"),
+        py::arg("capacity"), py::arg("ignore_index") = -100,
+        py::arg("launches") = 0);
+  // -> rows
+  m.def("masked_rows_gather", &hvd::gpu::MaskedRowsGather, py::arg("x"),
+        py::arg("idx"), py::arg("count"));
+  // -> dx
+  m.def("masked_rows_scatter", &hvd::gpu::MaskedRowsScatter,
+        py::arg("d_rows"), py::arg("rank"));
+  m.def("masked_rows_chunk", &hvd::gpu::MaskedRowsChunk);
+
   // ---- fused bias + GELU + dropout (None = absent bias) --------------------
   m.def("fused_bias_gelu_forward",
         [opt_tensor](at::Tensor u, py::object bias, double p, uint64_t seed,

@@ -185,6 +185,30 @@ std::vector<at::Tensor> FusedEmbBackward(at::Tensor dy, at::Tensor ids,
                                          at::Tensor rstd, double p,
                                          uint64_t seed, uint64_t offset);
 
+// ---- Compaction of the labelled rows; defined in rows.cc --------------------
+// The rows of x [M, H] whose label differs from ignore_index, gathered in
+// rising position (rows_kernels.hip), for the BERT MLM head.  labels:
+// contiguous, 16-B aligned int64 on a GPU, M = numel < 2^31; rows: contiguous,
+// 16-B aligned fp32 / fp16 / bf16 [n, H] with H * sizeof(T) a multiple of 16.
+// Anything else throws before the first launch.  Nothing is read by the host.
+// -> {idx [capacity] int32, rank [M] int32, row_labels [capacity] int64,
+// count [1] int32}: idx the position of the r-th labelled row (-1 from count
+// on), rank its inverse (-1 for an unlabelled row), row_labels the labels of
+// those rows (ignore_index from count on), count the number of labelled rows,
+// also when it exceeds capacity.  launches: 1 (every block recounts the
+// chunks before it), 2 (a launch of per-chunk counts first) or 0 (by length).
+std::vector<at::Tensor> MaskedRowsIndex(at::Tensor labels, int64_t capacity,
+                                        int64_t ignore_index,
+                                        int64_t launches);
+// -> rows [idx.numel(), H]: x[idx[r]] for r < count, zeros from count on;
+// every element NaN when count exceeds idx.numel().
+at::Tensor MaskedRowsGather(at::Tensor x, at::Tensor idx, at::Tensor count);
+// -> dx [rank.numel(), H]: d_rows[rank[r]] where 0 <= rank[r] < d_rows' rows,
+// else zeros; every element written once.
+at::Tensor MaskedRowsScatter(at::Tensor d_rows, at::Tensor rank);
+// Labels per block of the index build.
+int64_t MaskedRowsChunk();
+
 // ---- Fused bias + GELU + dropout; defined in gelu.cc -----------------------
 // out = dropout(gelu(u + bias), p) over the last dimension N of a contiguous
 // u (gelu_kernels.hip): N % 8 == 0, N >= 8, fp32 / fp16 / bf16, every tensor

@@ -712,5 +712,49 @@ hipError_t EmbScatterLaunch(const long long* sorted_ids,
                             float* dtok, float* dpos, long long M, int H,
                             long long V, int S, int P, hipStream_t stream);
 
+// ---- Compaction of the labelled rows (rows_kernels.hip) --------------------
+// A row r of labels [M] (int64) is labelled when labels[r] != ignore_index;
+// count is their number.  The kernels compact the labelled rows of x [M, H]
+// into rows [capacity, H] in rising position and scatter a gradient back.
+// Rows are copied as 16-B vectors whatever their dtype: row_bytes = H *
+// sizeof(T), a multiple of 16 up to kRowsMaxRowBytes, 1 <= M, capacity <=
+// kRowsMaxM and every pointer 16-B aligned, or the launchers return
+// hipErrorInvalidValue.  No host read, no memset, no atomics, no block waits
+// for another: results are bitwise reproducible.
+constexpr int kRowsChunk = 2048;      // labels per block of the index build
+constexpr int kRowsGatherRows = 4;    // output rows per wave of the gather
+constexpr long long kRowsMaxM = 2147483647LL;
+constexpr long long kRowsMaxRowBytes = 1LL << 24;
+// Up to this many chunks the index build is one launch in which the block of
+// chunk c counts the c chunks before it; past it a launch of per-chunk counts
+// goes first.
+constexpr int kRowsRecountMaxChunks = 4;
+
+int RowsIndexChunks(long long M);
+// True when RowsIndexLaunch for M labels needs `counts`.
+bool RowsIndexUsesCounts(long long M);
+// idx [capacity]: the position of the r-th labelled row, -1 in [count,
+// capacity).  rank [M]: r for a labelled row (also where r >= capacity), else
+// -1.  row_labels [capacity]: the labels of those rows, ignore_index in
+// [count, capacity).  count [1]: the number of labelled rows, also when it
+// exceeds capacity.  counts: null (one launch, blocks recount), or a
+// workspace of RowsIndexChunks(M) ints (two launches).
+hipError_t RowsIndexLaunch(const long long* labels, long long M,
+                           long long ignore_index, long long capacity,
+                           int* counts, int* idx, int* rank,
+                           long long* row_labels, int* count,
+                           hipStream_t stream);
+// rows[r] = x[idx[r]] for r < count, zeros for count <= r < capacity.  With
+// count > capacity every element of rows is NaN of dt (DT_F32, DT_F16,
+// DT_BF16), as is a row whose idx is outside [0, M).
+hipError_t RowsGatherLaunch(const void* x, const int* idx, const int* count,
+                            void* rows, long long M, long long capacity,
+                            long long row_bytes, int dt, hipStream_t stream);
+// dx[r] = d_rows[rank[r]] where 0 <= rank[r] < capacity, else zeros; every
+// element of dx [M, H] is written once.
+hipError_t RowsScatterLaunch(const void* d_rows, const int* rank, void* dx,
+                             long long M, long long capacity,
+                             long long row_bytes, hipStream_t stream);
+
 }  // namespace gpu
 }  // namespace hvd

@@ -13,7 +13,8 @@ import torch.nn.functional as F
 
 from horovod_amd.ops import (FusedDropoutAddLayerNorm, FusedLayerNorm,
                              FusedLinearGELU, embedding_layer_norm,
-                             self_attention, softmax_cross_entropy)
+                             gather_labelled_rows, self_attention,
+                             softmax_cross_entropy)
 
 
 class BertConfig:
@@ -211,10 +212,18 @@ class BertForPretraining(nn.Module):
         self.nsp = nn.Linear(cfg.hidden, 2)
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None,
-                add_mlm_bias=True):
+                add_mlm_bias=True, mlm_labels=None, max_predictions=None):
         """add_mlm_bias=False returns the MLM logits as the vocabulary GEMM
         leaves them (bf16 under autocast), for a loss that adds mlm_bias
-        itself: BertPretrainingLoss(fused=True)(..., mlm_bias=model.mlm_bias)."""
+        itself: BertPretrainingLoss(fused=True)(..., mlm_bias=model.mlm_bias).
+
+        mlm_labels [B, S]: the MLM head runs on the labelled positions only
+        (label != -100, horovod_amd.ops.gather_labelled_rows) and the call
+        returns (mlm_logits [capacity, V], nsp_logits, row_labels [capacity])
+        for BertPretrainingLoss(mlm_logits, nsp_logits, row_labels, ...).
+        capacity is B * max_predictions, with nothing read on the host; more
+        labelled positions than that in a batch make the logits NaN.  Without
+        max_predictions the count is read on the host."""
         if self.fused_emb:
             x = embedding_layer_norm(
                 input_ids, token_type_ids, self.tok_emb.weight,
@@ -232,18 +241,28 @@ class BertForPretraining(nn.Module):
         if attention_mask is not None:
             pad_mask = attention_mask == 0
         h = self.encoder(x, src_key_padding_mask=pad_mask)
+        rows, row_labels = h, None
+        if mlm_labels is not None:
+            capacity = None
+            if max_predictions is not None:
+                capacity = h.shape[0] * max_predictions
+            rows, row_labels = gather_labelled_rows(h, mlm_labels, capacity)
         # tied MLM head (weight sharing with tok_emb, BERT-standard)
-        mlm = self.mlm_transform(h) @ self.tok_emb.weight.t()
+        mlm = self.mlm_transform(rows) @ self.tok_emb.weight.t()
         if add_mlm_bias:
             mlm = mlm + self.mlm_bias
         nsp = self.nsp(h[:, 0])
+        if mlm_labels is not None:
+            return mlm, nsp, row_labels
         return mlm, nsp
 
 
 class BertPretrainingLoss(nn.Module):
     """The pretraining loss of BertForPretraining's two outputs: the MLM
     cross-entropy over mlm_logits.flatten(0, 1), where a label of -100 marks a
-    position that was not masked, plus the NSP cross-entropy.
+    position that was not masked, plus the NSP cross-entropy.  mlm_logits
+    [rows, V] with mlm_labels [rows], as a model called with mlm_labels
+    returns them, are taken as they are.
 
     fused: take the MLM term through horovod_amd.ops.softmax_cross_entropy,
     which reads the [B * S, V] logits in their own dtype instead of an fp32
@@ -265,7 +284,9 @@ class BertPretrainingLoss(nn.Module):
 
     def forward(self, mlm_logits, nsp_logits, mlm_labels, nsp_labels,
                 mlm_bias=None):
-        mlm_logits, mlm_labels = mlm_logits.flatten(0, 1), mlm_labels.flatten()
+        if mlm_logits.dim() > 2:
+            mlm_logits = mlm_logits.flatten(0, 1)
+        mlm_labels = mlm_labels.flatten()
         if self.fused:
             mlm = softmax_cross_entropy(mlm_logits, mlm_labels,
                                         ignore_index=-100, bias=mlm_bias)

@@ -12,6 +12,7 @@ from horovod_amd.ops.fused_gelu import (FusedLinearGELU,  # noqa: F401
                                         bias_gelu_dropout)
 from horovod_amd.ops.fused_attn import self_attention  # noqa: F401
 from horovod_amd.ops.fused_emb import embedding_layer_norm  # noqa: F401
+from horovod_amd.ops.masked_rows import gather_labelled_rows  # noqa: F401
 from horovod_amd.ops.fused_xent import (FusedCrossEntropyLoss,  # noqa: F401
                                         softmax_cross_entropy)
 from horovod_amd.ops.clip import clip_grad_norm_  # noqa: F401
